@@ -16,12 +16,21 @@ Other workloads (--config): C3 = kinetic FP with a GMM potential (d = 4, K = 8, 
 simulate + fused GMM residual over init/0T/terminal); C4 = kinetic McKean–Vlasov (d = 8, 2^21
 particles per GPU, one all-reduced mean field per update, + the KMV residual).
 
-After the timed region (untimed, C2): the drift tilde_F is recovered as the exact minimiser of the
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs DIR is given, and
+prints the result line; everything below that is not the headline figure runs only with --full.
+
+--dump-outputs DIR: after the timed steps, what the hot path returned in its LAST timed step is written as
+DIR/<name>.npy (float32 / float64; rank 0's arrays): the residual value and gradient and the reduced sums in
+full, the per-particle outputs (traj, tau, last) on a fixed seeded sample of DUMP_ROWS particles. The inputs
+(ensemble, Philox seed and counters) depend only on the arguments, so two builds compare output for output.
+
+With --full, after the timed region (untimed, C2): the drift tilde_F is recovered as the exact minimiser of the
 residual from the moments of all timed steps, with Richardson extrapolation over n = 100 / 200
 to cancel the O(dt) Euler–Maruyama bias; the CPU baseline — the NumPy
-restatement of sampling_utils.py in oracle/ — is timed on a bounded sample on rank 0.
+restatement of sampling_utils.py in oracle/ — is timed on a bounded sample on rank 0; the box's streaming-write
+ceiling is measured beside the roofline. C3 with --full adds the simulate-only and standalone-residual timings.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either under torch.distributed.run
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. For N > 1 either under torch.distributed.run
 (WORLD_SIZE must equal N, else the run exits non-zero) or plain, in which case bench.py starts the
 N-rank torch.distributed.run itself as a child process before touching the GPU. The line carries
 `ranks_seen` (the process group's size) and `backend`.
@@ -97,8 +106,15 @@ def parse():
     p.add_argument("--particles-total", type=int, default=0,
                    help="strong scaling: the job's particles (0 = 8 x the per-GPU count, the 8-GPU configuration)")
     p.add_argument("--n-steps", type=int, default=100)
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-recovery", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need (untimed): C2 the drift recovery, the CPU "
+                        "baselines and the box's streaming-write ceiling; C3 the simulate-only and standalone-residual "
+                        "timings. Off by default: a plain run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the hot path returned in its last timed step as DIR/<name>.npy (rank 0; "
+                        "per-particle outputs on a fixed seeded sample of particles)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-recovery", action="store_true", help="with --full: skip the drift recovery")
     p.add_argument("--recovery-passes", type=int, default=128,
                    help="ensembles per discretisation for the (untimed) drift recovery")
     p.add_argument("--cpu-particles", type=int, default=1 << 20)
@@ -165,16 +181,20 @@ def run_ramp(ramp, dev, seconds=RAMP_S, sync=None):
             return rounds
 
 
-def timed(step, K, W, dev, ramp=None):
+def timed(step, K, W, dev, ramp=None, reset=None):
     """Clock ramp, W untimed warmup steps, then K steps between barrier+synchronize; max over ranks.
     step(record) records record[0]/record[1] around the dominant kernel's launch.
     The ramp (untimed setup, like allocating the buffers) repeats the step's work for RAMP_S seconds
     first: an MI355X raises its clocks over the first ~0.1-0.3 s of sustained load (one box measured a
     20-step run 8 % below its 200-step rate without it; on another the ramp changed nothing).
-    ramp() (default: step(None)) must not feed any result of the run.
+    ramp() (default: step(None)) must not feed any result of the run: the ramp runs for a wall-clock time, so
+    a config whose ramp advances the Philox counter or other state passes reset(), called after the ramp, to
+    put that state back — the warmup and timed steps then see the same inputs in every run.
     Returns (ms per step, mean dominant-launch ms); the launch spread (min over ranks of the per-rank min,
     max over ranks of the median and of the max) goes to KERN_STATS for roofline.kernel_ms_*."""
     run_ramp(ramp or (lambda: step(None)), dev)
+    if reset is not None:
+        reset()
     for _ in range(W):
         step(None)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
@@ -194,6 +214,38 @@ def timed(step, K, W, dev, ramp=None):
                       kernel_ms_max=dist.allreduce_max_scalar(float(per.max()), device=dev),
                       kernel_launches_timed=int(K))
     return el * 1e3 / K, kern_ms
+
+
+DUMP_ROWS = 4096  # particles of a per-particle output that --dump-outputs keeps
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(a, rank, arrays, per_particle=()):
+    """--dump-outputs: rank 0 writes arrays[name] as DIR/<name>.npy, float32 / float64. The names in
+    per_particle map to (tensor, particle axis): with more than DUMP_ROWS particles a fixed seeded sample of
+    them is kept (sorted ids, the same in every run with the same particle count)."""
+    if not a.dump_outputs or rank != 0:
+        return
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    out = {k: v for k, v in arrays.items() if v is not None}
+    for name, (t, axis) in dict(per_particle).items():
+        if t is None:
+            continue
+        N = t.shape[axis]
+        if N > DUMP_ROWS:
+            ids = np.sort(np.random.default_rng(0x0D0E).choice(N, DUMP_ROWS, replace=False))
+            out["particle_ids"] = torch.as_tensor(ids, dtype=torch.float64)
+            t = t.index_select(axis, torch.as_tensor(ids, device=t.device))
+        out[name] = t
+    total = 0
+    for name, t in out.items():
+        arr = t.detach().cpu().numpy()
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            sys.exit(f"bench.py: --dump-outputs would exceed {DUMP_MAX_BYTES} bytes at {name}")
+        np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
 
 
 def write_ceiling(buf, reps=5):
@@ -273,7 +325,8 @@ def run_c2(a, rank, world, dev):
             "moments": torch.empty((3, native.moment_len(2 * d)), device=dev, dtype=torch.float64)}
     mom_total = torch.zeros((3, native.moment_len(2 * d)), device=dev, dtype=torch.float64)
     counter = [0]
-    last_res = [None]
+    last_res = [None, None]
+    recover = a.full and not a.no_recovery
 
     def step(record):
         if record is not None:
@@ -285,13 +338,18 @@ def run_c2(a, rank, world, dev):
         counter[0] = (counter[0] + n + 1) & 0xFFFFFFFF
         mom = dist.allreduce_sum(r["moments"])
         last_res[0] = native.residual_kfp_quadratic(mom, theta, F, gamma, T)
-        mom_total.add_(mom)
+        last_res[1] = mom
+        if recover:  # the timed steps' moments feed the drift recovery
+            mom_total.add_(mom)
 
     def ramp():  # the same launch, results discarded (mom_total feeds the drift recovery)
         native.sde_simulate(z0, n, T / n, gamma, pot, seed=seed, counter_offset=counter[0], particle_offset=poff,
                             moments=True, out=bufs)
 
     ms, kern_ms = timed(step, a.steps, a.warmup, dev, ramp=ramp)
+    dump_outputs(a, rank, {"moments_local": bufs["moments"], "moments": last_res[1],
+                           "residual_out": last_res[0][0], "residual_grad": last_res[0][1]},
+                 {"traj": (bufs["traj"], 1), "tau": (bufs["tau"], 1), "last": (bufs["last"], 0)})
     value = total * (n + 1) / (ms / 1e3)
     cfg = {"workload": "C2 kinetic OU d=4: EM simulate (traj+tau+last, fused moments) + KFP residual "
                        "value_and_grad", "dim": d, "n_steps": n, "particles_per_gpu": N, "particles_total": total, "total_time": T,
@@ -300,10 +358,11 @@ def run_c2(a, rank, world, dev):
                       "sde_simulate_kernel<4,QUADRATIC,moments,staged> (+ its slab reduce)",
                       traffic_from_profiles("sde_simulate_C2_bytes_per_launch") if (N, n) == (1 << 21, 100) else None)
     out["loss"] = float(last_res[0][0][0].item())
-    ceil = dist.allreduce_max_scalar(-write_ceiling(bufs["traj"]), device=dev) * -1.0  # min over ranks
-    out["roofline"]["box_write_ceiling_GBps"] = ceil
-    out["roofline"]["frac_of_box_write_ceiling"] = out["roofline"]["achieved"] / ceil
-    if not a.no_recovery:
+    if a.full:
+        ceil = dist.allreduce_max_scalar(-write_ceiling(bufs["traj"]), device=dev) * -1.0  # min over ranks
+        out["roofline"]["box_write_ceiling_GBps"] = ceil
+        out["roofline"]["frac_of_box_write_ceiling"] = out["roofline"]["achieved"] / ceil
+    if recover:
         # untimed; a fixed Monte-Carlo budget (independent of --steps) of fresh moments-only passes,
         # on top of the timed steps' moments, at n = 100 and n = 200
         passes = max(a.recovery_passes, a.steps + a.warmup)
@@ -318,7 +377,7 @@ def run_c2(a, rank, world, dev):
         out["drift_recovery"] = ("max |S - tilde_F|, S = K + K^T the exact residual minimiser from the EM moments, "
                                  "Richardson (8 S(n=400) - 6 S(n=200) + S(n=100)) / 3, "
                                  f"{passes * total} trajectories per level")
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU baseline: rank 0 at N = 1 only
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:  # the CPU baseline: rank 0 at N = 1 only
         from oracle import cpu_baseline as cb
         from example_problems.kinetic_fokker_planck_example_OU import problem_matrix as pm
         ups1, secs1 = cb.single(F, d, n, T, gamma, a.cpu_particles)
@@ -387,7 +446,7 @@ def run_c3(a, rank, world, dev):
     Ng = total
     desc = native.kfp_gmm_desc(d, K, mus, gamma, T, Ng, Ng, Ng * n)
     counter = [0]
-    last_out = [None]
+    last_out = [None, None]
 
     def step(record):
         if record is not None:
@@ -399,8 +458,14 @@ def run_c3(a, rank, world, dev):
         counter[0] = (counter[0] + n + 1) & 0xFFFFFFFF
         acc = dist.allreduce_sum(r["acc"])
         last_out[0] = native.residual_kfp_gmm_finalize(desc, acc)
+        last_out[1] = acc
 
-    ms, kern_ms = timed(step, a.steps, a.warmup, dev)
+    def reset():  # the ramp ran step() a wall-clock number of times
+        counter[0] = 0
+
+    ms, kern_ms = timed(step, a.steps, a.warmup, dev, reset=reset)
+    dump_outputs(a, rank, {"acc": last_out[1], "residual_out": last_out[0][0], "residual_grad": last_out[0][1]},
+                 {"traj": (bufs["traj"], 1), "tau": (bufs["tau"], 1), "last": (bufs["last"], 0)})
     value = total * (n + 1) / (ms / 1e3)
     cfg = {"workload": "C3 kinetic FP, GMM potential K=8, d=4: EM simulate (traj+tau+last) with the GMM-model KFP "
                        "residual value_and_grad over init/0T/terminal fused into the same launch",
@@ -416,6 +481,8 @@ def run_c3(a, rank, world, dev):
     out["loss"] = float(last_out[0][0][0].item())
     if (N, n) == (1 << 22, 100):
         out["roofline"]["valu_issue"] = c3_valu_issue(kern_ms, N, n)
+    if not a.full:
+        return out
 
     # untimed context: the same simulator without the residual, and the standalone residual kernel
     # (the offline-dataset path) over the same trajectory, each timed with events on its stream
@@ -473,6 +540,7 @@ def run_c4(a, rank, world, dev):
     side = torch.cuda.Stream(device=dev)
     ev = {"sums": [], "res": []}
     sums_next = [None]  # rank-local mean-path sums of the next simulate, from the previous step's KMV pass
+    final = {}  # what the last step returned (--dump-outputs)
 
     def step(record):
         coef = coef_next[0].to(dev, non_blocking=True)
@@ -538,7 +606,8 @@ def run_c4(a, rank, world, dev):
             ev["sums"].append((e0, record[0]))
             ev["res"].append((record[1], e3))
         both = dist.allreduce_sum(torch.cat([mom.reshape(-1), wst.reshape(-1)]))
-        native.residual_kmv(both[: mom.numel()].view_as(mom), both[mom.numel():].view_as(wst), theta, A, gamma)
+        res = native.residual_kmv(both[: mom.numel()].view_as(mom), both[mom.numel():].view_as(wst), theta, A, gamma)
+        final.update(bufs=bufs, wrote_traj=not kmv_in_sim, mom=mom, wst=wst, res=res)
         coef_next[0] = host_coef(counter[0])
 
     # Two-stream pipeline (world 1, --c4-pipeline; slower, kept for A/B): the simulate of step k+1 depends on z0 and the noise stream only — not on
@@ -591,14 +660,35 @@ def run_c4(a, rank, world, dev):
                     ev["sums"].append((e0, record[0]))
                     ev["res"].append((e2, e3))
                 both = dist.allreduce_sum(torch.cat([mom.reshape(-1), wst.reshape(-1)]))
-                native.residual_kmv(both[: mom.numel()].view_as(mom), both[mom.numel():].view_as(wst), theta, A,
-                                    gamma)
+                res = native.residual_kmv(both[: mom.numel()].view_as(mom), both[mom.numel():].view_as(wst), theta,
+                                          A, gamma)
+                final.update(bufs=b, wrote_traj=True, mom=mom, wst=wst, res=res)
                 ev_done = torch.cuda.Event()
                 ev_done.record()
                 pass_done[k] = ev_done
             coef_next[0] = host_coef(counter[0])
 
-    ms, kern_ms = timed(step, a.steps, a.warmup, dev)
+    def reset():
+        # the ramp ran step() a wall-clock number of times: back to counter 0, with the first simulate's
+        # mean-path sums ready where the steady state carries them from the step before
+        torch.cuda.synchronize()
+        counter[0] = 0
+        coef_next[0] = host_coef(0)
+        ev["sums"].clear()
+        ev["res"].clear()
+        if sums_next[0] is not None:
+            desc0, keep0 = native.mf_desc(N, d, n, T / n, gamma, A, seed=key.seed, counter_offset=0,
+                                          particle_offset=poff)
+            sums_next[0] = native.mf_sums(desc0, z0)
+            torch.cuda.synchronize()
+            del keep0
+
+    ms, kern_ms = timed(step, a.steps, a.warmup, dev, reset=reset)
+    fb = final["bufs"]
+    dump_outputs(a, rank, {"kmv_moments": final["mom"], "kmv_weight_sums": final["wst"],
+                           "residual_out": final["res"][0], "residual_grad": final["res"][1]},
+                 {"last": (fb["last"], 0), "traj": (fb["traj"] if final["wrote_traj"] else None, 1),
+                  "tau": (fb["tau"] if final["wrote_traj"] else None, 1)})
     value = total * (n + 1) / (ms / 1e3)
     cfg = {"workload": "C4 kinetic McKean-Vlasov quadratic interaction d=8: interacting-particle EM (closed-form "
                        "mean path from one all-reduced noise/z0 sum per simulate, all updates in registers) + KMV "
@@ -687,6 +777,7 @@ def run_c5(a, rank, world, dev):
             "last": torch.empty((N, 2 * d), device=dev)}
     counter = [0]
     sim_ev = []
+    final = {}  # what the last step returned (--dump-outputs)
 
     def step(record):
         e0 = torch.cuda.Event(enable_timing=True) if record is not None else None
@@ -705,9 +796,16 @@ def run_c5(a, rank, world, dev):
         if record is not None:
             record[1].record()
         both = dist.allreduce_sum(torch.cat([acc, grad.double()]))
-        native.kfp_terms_finalize(both[: acc.numel()], both[acc.numel():].float(), gamma)
+        final["grad"] = both[acc.numel():].float()
+        final["acc"] = both[: acc.numel()]
+        final["out"] = native.kfp_terms_finalize(final["acc"], final["grad"], gamma)
 
-    ms, kern_ms = timed(step, a.steps, a.warmup, dev)
+    def reset():  # the ramp ran step() a wall-clock number of times
+        counter[0] = 0
+
+    ms, kern_ms = timed(step, a.steps, a.warmup, dev, reset=reset)
+    dump_outputs(a, rank, {"acc": final["acc"], "residual_grad": final["grad"], "residual_out": final["out"]},
+                 {"traj": (bufs["traj"], 1), "tau": (bufs["tau"], 1), "last": (bufs["last"], 0)})
     rows = N + 2 * nb
     # 24P per 0T row (value, ∂v, ∂v² Taylor streams, the ∇x reverse and the θ reverse), 12P per
     # initial / terminal row — the reference evaluates only ∇V·v there (kinetic_fokker_planck.py:34-39)

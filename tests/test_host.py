@@ -313,6 +313,44 @@ def test_bench_refuses_mismatched_world_size():
         assert r.returncode != 0 and "{" not in r.stdout, (r.stdout, r.stderr[-2000:])
 
 
+def test_bench_dump_outputs_and_full_defaults(tmp_path, monkeypatch):
+    """bench.py: --full is off and --dump-outputs unset by default; dump_outputs writes float32 / float64 .npy
+    files on rank 0 only, keeps small per-particle outputs whole and cuts large ones to the same DUMP_ROWS sorted
+    particle ids in every call (on whichever axis holds the particles), and converts integer outputs to float64."""
+    import sys
+    import torch
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "d")
+    N = bench.DUMP_ROWS + 37
+    traj = torch.arange(3 * N * 2, dtype=torch.float32).view(3, N, 2)
+    last = torch.arange(N * 2, dtype=torch.float32).view(N, 2)
+    small = torch.arange(10, dtype=torch.float32).view(5, 2)
+    for k in ("d", "e"):
+        a.dump_outputs = str(tmp_path / k)
+        bench.dump_outputs(a, 0, {"out": torch.tensor([1.5], dtype=torch.float64), "count": torch.tensor([3, 4]),
+                                  "absent": None},
+                           {"traj": (traj, 1), "last": (last, 0), "small": (small, 0), "none": (None, 1)})
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in sorted(os.listdir(tmp_path / "d"))}
+    assert sorted(got) == ["count", "last", "out", "particle_ids", "small", "traj"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["count"].dtype == np.float64 and got["count"].tolist() == [3.0, 4.0] and got["out"].tolist() == [1.5]
+    ids = got["particle_ids"].astype(np.int64)
+    assert ids.shape == (bench.DUMP_ROWS,) and np.all(np.diff(ids) > 0) and ids.min() >= 0 and ids.max() < N
+    assert np.array_equal(got["traj"], traj.numpy()[:, ids]) and np.array_equal(got["last"], last.numpy()[ids])
+    assert np.array_equal(got["small"], small.numpy())
+    assert sum(v.nbytes for v in got.values()) <= bench.DUMP_MAX_BYTES
+    for f in os.listdir(tmp_path / "d"):
+        assert np.array_equal(np.load(tmp_path / "e" / f), got[f[:-4]]), f
+    a.dump_outputs = str(tmp_path / "r1")
+    bench.dump_outputs(a, 1, {"out": torch.zeros(1)})
+    assert not os.path.exists(tmp_path / "r1")
+
+
 def test_oracle_under_asan():
     """the host AddressSanitizer + UBSan build of the C oracle (oracle/Makefile `asan`,
     oracle/asan_driver.c) runs every oracle entry point on ragged inputs and the Philox KATs clean."""
