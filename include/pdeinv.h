@@ -46,6 +46,8 @@ extern "C" {
 #endif
 
 #define PDEINV_ABI_VERSION 10  /* 10: pdeinv_sde_simulate_mf_kmv; 9: pdeinv_ou_exact_sample, pdeinv_kmv_mlp_path */
+/* Added within version 10 (new entry points only, nothing existing changed): pdeinv_realnvp_time_derivs,
+ * pdeinv_realnvp_time_derivs_sets, pdeinv_realnvp_time_impl, pdeinv_kmv_weights_from_ds(_workspace_bytes). */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -317,6 +319,16 @@ size_t pdeinv_kmv_weights_workspace_bytes(int64_t n_sets, int64_t n_rows, int32_
 int pdeinv_kmv_weights(int32_t dim, float gamma, const float* d_coef, const float* d_z,
                        int64_t n_sets, int64_t n_rows, int64_t set_stride, int64_t ld,
                        float* d_ds, void* d_workspace, double* d_out, void* stream);
+
+/* The reduction half of pdeinv_kmv_weights with the per-particle pair given instead of computed from d_coef:
+ * d_ds [n_sets][n_rows][2] = (ds log rho, ds2 log rho), e.g. a learned density's from
+ * pdeinv_realnvp_time_derivs_sets. Per stamp d_out = [sum c, sum c x, sum c x_i x_j (i <= j)], c = ds2 + ds^2 +
+ * gamma ds: the same fp32-per-block / fp64-across-blocks fixed-order reduction (deterministic), the `wst` of
+ * pdeinv_residual_kmv. d_ds 8-byte aligned. Workspace: pdeinv_kmv_weights_from_ds_workspace_bytes(). */
+size_t pdeinv_kmv_weights_from_ds_workspace_bytes(int64_t n_sets, int64_t n_rows, int32_t dim);
+int pdeinv_kmv_weights_from_ds(int32_t dim, float gamma, const float* d_ds, const float* d_z, int64_t n_sets,
+                               int64_t n_rows, int64_t set_stride, int64_t ld, void* d_workspace, double* d_out,
+                               void* stream);
 
 /* Fused pdeinv_moments_batched(m = 2d) + pdeinv_kmv_weights: one read of each row z = [x, v] gives
  * d_mom [n_sets][pdeinv_moment_len(2d)] and d_wstats [n_sets][pdeinv_moment_len(d)] (the same sums,
@@ -594,6 +606,32 @@ int64_t pdeinv_realnvp_param_count(const pdeinv_realnvp_desc* desc);
 int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_t,
                               int64_t t_stride, const float* d_x, int64_t n, int64_t ld_x, float* d_out,
                               void* stream);
+
+/* Time derivatives of the log-density (what jax.grad(log_density_fn, 0), taken twice, gives the reference's KMV
+ * residual, kinetic_mckean_vlasov.py:57-72): per sample, in one pass, d_logp[i] = log p_{t_i}(x_i) (nullable) and
+ * d_ds[2 i], d_ds[2 i + 1] = (d/dt, d2/dt2) of it, by second-order forward mode in t through the whole model.
+ * Same envelope as pdeinv_realnvp_logdensity. At the kinks: relu g' = [z > 0], g'' = 0; celu / elu (g', g'') =
+ * (1, 0) for z > 0, (e^z, e^z) for z <= 0. ignore_time: the derivatives are exactly 0. Deterministic (plain
+ * stores, no atomics). d_ds must be 8-byte aligned. n == 0 is a no-op.
+ * _sets: the (d_z, n_sets, n_rows, set_stride, ld) view of pdeinv_kmv_weights / pdeinv_residual_kmv_mlp (ld == 0:
+ * 2 dim); stamp s's rows share d_tau[s]; outputs at [s * n_rows + r], so d_ds [n_sets][n_rows][2] is the layout
+ * pdeinv_residual_kmv_mlp and pdeinv_kmv_weights_from_ds consume. Bit-identical to the per-sample entry point. */
+int pdeinv_realnvp_time_derivs(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_t,
+                               int64_t t_stride, const float* d_x, int64_t n, int64_t ld_x, float* d_logp,
+                               float* d_ds, void* stream);
+int pdeinv_realnvp_time_derivs_sets(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_tau,
+                                    const float* d_z, int64_t n_sets, int64_t n_rows, int64_t set_stride, int64_t ld,
+                                    float* d_logp, float* d_ds, void* stream);
+
+/* Path selector of the two entry points above, for tests and measurements (process-wide): impl 0 = AUTO, 1 = the
+ * general per-thread path (the whole envelope), 2 = the matrix-core path (celu / elu, dim <= 4, 4 <= E <= 12, no
+ * ignore_time; other descriptors then fail with UNSUPPORTED); any other impl (e.g. -1) changes nothing. Returns
+ * the path `desc` takes under the selector now in force: 0 general, 1 matrix-core, UNSUPPORTED (desc NULL: the
+ * selector). AUTO takes the matrix-core path only where it measured faster. The two paths agree to fp32 rounding. */
+#define PDEINV_NVP_TIME_AUTO 0
+#define PDEINV_NVP_TIME_GENERAL 1
+#define PDEINV_NVP_TIME_MATRIX 2
+int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* desc, int32_t impl);
 
 /* Maximum-likelihood value_and_grad of the flow (replaces jax.value_and_grad(loss_fn) in
  * core/log_density_estimation.py:47-58): *d_loss = -mean_i log p_{t_i}(x_i), d_grad[param_count]

@@ -50,13 +50,34 @@ def create_custom_schedule(lr, T0, T1):
     return schedule
 
 
-def estimate_log_density(cfg, pde_instance, rng, num_epochs: int = 20000, frequency: int = 100, verbose=True):
+def make_log_density_fn(model: RealNVP, params):
+    """log_density_fn(t, x) of a flow and its parameters, as estimate_log_density returns it: .model, .params and
+    .partial_s(t, x) -> (ds log p, ds2 log p) (pdeinv_realnvp_time_derivs)."""
+    def log_density_fn(t, x):
+        return model.apply(params, t, x)
+
+    def partial_s(t, x):
+        _, d1, d2 = model.time_derivatives(params, t, x)
+        return d1, d2
+
+    log_density_fn.params = params
+    log_density_fn.model = model
+    log_density_fn.partial_s = partial_s
+    return log_density_fn
+
+
+def estimate_log_density(cfg, pde_instance, rng, num_epochs: int = 20000, frequency: int = 100, verbose=True,
+                         dataset=None):
     """Train the flow on pde_instance.dataset (offline "0T" trajectories and their tau) and return
-    log_density_fn(t, x) (:13-100). Returns (log_density_fn, history of mean losses per interval)."""
+    log_density_fn(t, x) (:13-100) with .history (mean loss per interval), .params, .model (the RealNVP) and
+    .partial_s(t, x) -> (ds log p, ds2 log p) (the time derivatives the KMV residual weights Phi with,
+    kinetic_mckean_vlasov.py:57-72). `dataset` (optional): {"0T_tm": time-major trajectories [n_time, n_traj,
+    >= dim], "tau_0T": [n_traj, n_time]} to train on instead of pde_instance.dataset, e.g. a KMV instance's own."""
     rngs = dict(zip(["model_init", "train"], prng.split(rng, 2)))
     dim = int(cfg.pde_instance.domain_dim)
     model = create_normalizing_flow_fn(pde_instance.distribution_initial_x.logdensity, dim)
-    dataset = pde_instance.dataset
+    if dataset is None:
+        dataset = pde_instance.dataset
     traj_tm = dataset["0T_tm"]                       # [n_time, n_traj, 2d] (time-major)
     dev = traj_tm.device
     params = model.init(rngs["model_init"], 0.0, np.zeros(dim), device=dev)
@@ -89,9 +110,6 @@ def estimate_log_density(cfg, pde_instance, rng, num_epochs: int = 20000, freque
             if verbose:
                 print(f"Epoch {epoch + 1}, Loss: {mean}")
 
-    def log_density_fn(t, x):
-        return model.apply(params, t, x)
-
+    log_density_fn = make_log_density_fn(model, params)
     log_density_fn.history = history
-    log_density_fn.params = params
     return log_density_fn

@@ -123,6 +123,20 @@ class RealNVP:
         out = native.realnvp_logdensity(self._desc, flat, tt, rows)
         return out[0] if single else out
 
+    def time_derivatives(self, params, t, x):
+        """(log p_t(x), d/dt log p_t(x), d2/dt2 log p_t(x)) — what jax.grad(log_density_fn, 0) taken twice gives in
+        the reference — in one pass of the HIP kernel `pdeinv_realnvp_time_derivs` (second-order forward mode in
+        t). Unbatched / batched like `apply`."""
+        flat = params["params"] if isinstance(params, dict) else params
+        x = torch.as_tensor(x, dtype=torch.float32, device=flat.device)
+        single = x.dim() == 1
+        rows = x.reshape(1, -1) if single else x
+        tt = torch.as_tensor(t, dtype=torch.float32, device=flat.device).reshape(-1)
+        logp, ds = native.realnvp_time_derivs(self._desc, flat, tt, rows)
+        if single:
+            return logp[0], ds[0, 0], ds[0, 1]
+        return logp, ds[:, 0], ds[:, 1]
+
     def value_and_grad(self, params, t, x):
         """(loss, grad) with loss = -mean_i log p_{t_i}(x_i) and grad flat like params
         (log_density_estimation.py:47-58), on the HIP kernel. celu / elu flows only."""

@@ -106,6 +106,34 @@ __global__ __launch_bounds__(kBlock) void kmv_weights_kernel(float gamma, const 
                        gridDim.x);
 }
 
+// The reduction half of kmv_weights_kernel: the per-particle (ds log rho, ds2 log rho) are given
+// (ds [n_sets][n_rows][2], e.g. a learned density's, pdeinv_realnvp_time_derivs_sets) instead of computed
+// from the Gaussian coefficients. Same weight, same accumulation and slab layout.
+template <int D>
+__global__ __launch_bounds__(kBlock) void kmv_weights_from_ds_kernel(float gamma, const float* __restrict__ ds,
+                                                                     const float* __restrict__ z, int64_t n_rows,
+                                                                     int64_t set_stride, int64_t ld,
+                                                                     float* __restrict__ partials) {
+  const int t = blockIdx.y;
+  MomentAcc<D> acc;
+  acc.zero();
+  const float* base = z + (int64_t)t * set_stride;
+  const f32x2* dst = reinterpret_cast<const f32x2*>(ds) + (int64_t)t * n_rows;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x; r < n_rows; r += stride) {
+    const float* row = base + r * ld;
+    float x[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = row[k];
+    const f32x2 q = dst[r];
+    const float w = q[1] + q[0] * q[0] + gamma * q[0];  // kinetic_mckean_vlasov.py:243-248
+    acc.add(x, w);
+  }
+  __shared__ float lds[kWavesPerBlock * moment_len(D)];
+  block_reduce_to_slab(acc.v, moment_len(D), lds, partials + (int64_t)t * moment_len(D) * gridDim.x, blockIdx.x,
+                       gridDim.x);
+}
+
 // Fused per-time-stamp pass: one read of each row z = [x, v] (2D floats) yields both the moments of
 // z (the moments_batched sums) and the c-weighted sums of x (the kmv_weights sums): the McKean–Vlasov
 // residual then reads its 2^21 x 100 x 64 B trajectory once instead of 1.5 times. Slab columns of set
@@ -544,6 +572,39 @@ extern "C" int pdeinv_kmv_weights(int32_t D, float gamma, const float* coef, con
       return fail(PDEINV_ERR_UNSUPPORTED, "kmv_weights: dim must be one of 1-8, 10, 12, 16");
   }
   int rc = check_launch("kmv_weights_kernel");
+  if (rc) return rc;
+  launch_slab_reduce(p, bx, (int)(n_sets * moment_len(D)), out, st);
+  return check_launch("slab_reduce_kernel");
+}
+
+extern "C" size_t pdeinv_kmv_weights_from_ds_workspace_bytes(int64_t n_sets, int64_t n_rows, int32_t dim) {
+  return pdeinv_kmv_weights_workspace_bytes(n_sets, n_rows, dim);
+}
+
+extern "C" int pdeinv_kmv_weights_from_ds(int32_t D, float gamma, const float* ds, const float* z, int64_t n_sets,
+                                          int64_t n_rows, int64_t set_stride, int64_t ld, void* ws, double* out,
+                                          void* stream) {
+  PDEINV_REQUIRE(D >= 1 && D <= 16, PDEINV_ERR_UNSUPPORTED, "kmv_weights_from_ds: dim must be in [1, 16]");
+  PDEINV_REQUIRE(n_sets >= 1 && n_sets <= 65535 && n_rows >= 0, PDEINV_ERR_INVALID,
+                 "kmv_weights_from_ds: need 1 <= n_sets <= 65535, n_rows >= 0");
+  if (ld == 0) ld = 2 * D;
+  PDEINV_REQUIRE(ld >= D && set_stride >= 0, PDEINV_ERR_INVALID, "kmv_weights_from_ds: bad strides");
+  PDEINV_REQUIRE(out && ws && (n_rows == 0 || (z && ds)), PDEINV_ERR_INVALID, "kmv_weights_from_ds: null pointer");
+  PDEINV_REQUIRE(((uintptr_t)ds & 7) == 0 && ((uintptr_t)z & 3) == 0 && ((uintptr_t)ws & 3) == 0 &&
+                     ((uintptr_t)out & 7) == 0,
+                 PDEINV_ERR_INVALID, "kmv_weights_from_ds: misaligned pointer (d_ds and d_out need 8 bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  const int bx = batched_bx(n_sets, n_rows);
+  const dim3 g(bx, (unsigned)n_sets);
+  float* p = (float*)ws;
+  switch (D) {
+#define CASE(DD) case DD: hipLaunchKernelGGL(kmv_weights_from_ds_kernel<DD>, g, dim3(kBlock), 0, st, gamma, ds, z, n_rows, set_stride, ld, p); break;
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(10) CASE(12) CASE(16)
+#undef CASE
+    default:
+      return fail(PDEINV_ERR_UNSUPPORTED, "kmv_weights_from_ds: dim must be one of 1-8, 10, 12, 16");
+  }
+  int rc = check_launch("kmv_weights_from_ds_kernel");
   if (rc) return rc;
   launch_slab_reduce(p, bx, (int)(n_sets * moment_len(D)), out, st);
   return check_launch("slab_reduce_kernel");

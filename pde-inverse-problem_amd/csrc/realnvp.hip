@@ -957,6 +957,9 @@ __global__ __launch_bounds__(kBlock, PK ? PDEINV_NVW_PK : PDEINV_NVW) void realn
 // lane), then the splits in order. Column c of parts is reference parameter c (n_params: the loss),
 // read from slab column nv_slab_col(c). On the last chunk grad[c] = scale * acc[c] (c < n_params) and
 // loss = scale * acc[n_params].
+#ifndef PDEINV_NVP_TIME_AUTO_MFMA
+#define PDEINV_NVP_TIME_AUTO_MFMA 1  // by measurement: faster than the general path on both batches
+#endif
 constexpr int kNvSplits = 16;
 __global__ __launch_bounds__(kBlock) void nvp_slab_split_kernel(const float* __restrict__ slab_base, int rows,
                                                                  int64_t ld, NvSlabMap map, int64_t n_cols,
@@ -1002,6 +1005,545 @@ __global__ __launch_bounds__(kBlock) void nvp_grad_reduce_kernel(const double* _
     if (last) {
       if (c < n_params) grad[c] = (float)(scale * v);
       else *loss = (float)(scale * v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Time derivatives of the log-density: (log p_t(x), d/dt, d2/dt2) per sample in one pass, by second-order
+// forward mode in t through the whole model (the KMV residual's weight c = ds2 + ds^2 + gamma ds,
+// kinetic_mckean_vlasov.py:57-72, 86-91, for a learned density; the reference takes jax.grad(., 0) twice).
+// Every t-dependent quantity is three streams [value, d/dt, d2/dt2]: dense layers act on the three alike
+// (bias on the value only: one weight fetch feeds three FMAs), y = g(z) maps them by
+//   y' = g'(z) z',  y'' = g''(z) z'^2 + g'(z) z'',
+// products by Leibniz. Kinks: relu g' = [z > 0], g'' = 0; celu / elu (g', g'') = (1, 0) for z > 0 and
+// (e^z, e^z) for z <= 0. General path: one thread per sample on the VALU, like realnvp_logdensity_kernel
+// (weights at wave-uniform addresses); every register array is indexed by unrolled loop counters only (the
+// runtime widths E and in_dim guard wave-uniform branches). Plain stores, no atomics: deterministic.
+// ---------------------------------------------------------------------------------------------
+// (g(z), g'(z), g''(z)) on the hardware exp2 / rcp
+// (ACT is a template parameter down to here: a runtime switch is if-converted into all seven evaluations)
+template <int ACT>
+__device__ __forceinline__ void nvp_act_d2(float z, float& g, float& g1, float& g2) {
+  switch (ACT) {
+    case PDEINV_ACT_CELU:
+    case PDEINV_ACT_ELU: {
+      const float e = nv_exp(fminf(z, 0.f));
+      const bool pos = z > 0.f;
+      g = pos ? z : e - 1.f;
+      g1 = pos ? 1.f : e;
+      g2 = pos ? 0.f : e;
+      break;
+    }
+    case PDEINV_ACT_RELU:
+      g = fmaxf(z, 0.f);
+      g1 = z > 0.f ? 1.f : 0.f;
+      g2 = 0.f;
+      break;
+    case PDEINV_ACT_TANH:
+      g = nv_tanh(z);
+      g1 = 1.f - g * g;
+      g2 = -2.f * g * g1;
+      break;
+    case PDEINV_ACT_SILU: {
+      const float s = __builtin_amdgcn_rcpf(1.f + nv_exp(-z)), q = s * (1.f - s);
+      g = z * s;
+      g1 = fmaf(z, q, s);
+      g2 = q * fmaf(z, 1.f - 2.f * s, 2.f);
+      break;
+    }
+    case PDEINV_ACT_SOFTPLUS: {
+      const float s = __builtin_amdgcn_rcpf(1.f + nv_exp(-z));
+      g = fmaxf(z, 0.f) + log1pf(nv_exp(-fabsf(z)));
+      g1 = s;
+      g2 = s * (1.f - s);
+      break;
+    }
+    default: {  // gelu, tanh approximation: g = z (1 + tanh u) / 2, u = c (z + a z^3)
+      const float c = 0.7978845608028654f, a = 0.044715f;
+      const float u = c * (z + a * z * z * z), u1 = c * fmaf(3.f * a * z, z, 1.f), u2 = 6.f * c * a * z;
+      const float th = nv_tanh(u), q = 1.f - th * th;
+      const float th1 = q * u1, th2 = q * u2 - 2.f * th * q * u1 * u1;
+      g = 0.5f * z * (1.f + th);
+      g1 = 0.5f * (1.f + th) + 0.5f * z * th1;
+      g2 = fmaf(0.5f * z, th2, th1);
+    }
+  }
+}
+
+// The three streams of a dense layer out = act?(b + in @ W) in pieces: bias (value stream only), the rows of one
+// input block (rows i >= n_in of the NI-wide block are not read; one weight fetch feeds three FMAs), activation.
+template <int NO>
+__device__ __forceinline__ void dense3_bias(const float* __restrict__ b, float (&out)[3][NO]) {
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    out[0][o] = b[o];
+    out[1][o] = 0.f;
+    out[2][o] = 0.f;
+  }
+}
+template <int NI, int NO>
+__device__ __forceinline__ void dense3_rows(const float* __restrict__ W, const float (&in)[3][NI], int n_in,
+                                            float (&out)[3][NO]) {
+  asm volatile("" ::: "memory");  // no weight fetches hoisted across dense layers (register pressure)
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    if (i < n_in) {
+#pragma unroll
+      for (int o = 0; o < NO; ++o) {
+        const float w = W[i * NO + o];
+        out[0][o] = fmaf(in[0][i], w, out[0][o]);
+        out[1][o] = fmaf(in[1][i], w, out[1][o]);
+        out[2][o] = fmaf(in[2][i], w, out[2][o]);
+      }
+    }
+  }
+}
+template <int ACT, int NO>
+__device__ __forceinline__ void dense3_act(float (&out)[3][NO]) {
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    float g, g1, g2;
+    nvp_act_d2<ACT>(out[0][o], g, g1, g2);
+    const float z1 = out[1][o];
+    out[0][o] = g;
+    out[2][o] = fmaf(g2 * z1, z1, g1 * out[2][o]);
+    out[1][o] = g1 * z1;
+  }
+}
+
+// BasicMLP over the input [xm (D) | temb (n_t)] kept as its two blocks
+template <int D, int ACT>
+__device__ __forceinline__ const float* basic_mlp3(const float* p, const float (&xm)[3][D], const float (&temb)[3][16],
+                                                   int n_t, float (&out)[3][D]) {
+  float h0[3][8], h1[3][16], h2[3][16];
+  const int n_in = D + n_t;
+  dense3_bias<8>(p + n_in * 8, h0);
+  dense3_rows<D, 8>(p, xm, D, h0);
+  dense3_rows<16, 8>(p + D * 8, temb, n_t, h0);
+  dense3_act<ACT, 8>(h0);
+  p += n_in * 8 + 8;
+  dense3_bias<16>(p + 8 * 16, h1);
+  dense3_rows<8, 16>(p, h0, 8, h1);
+  dense3_act<ACT, 16>(h1);
+  p += 8 * 16 + 16;
+  dense3_bias<16>(p + 16 * 16, h2);
+  dense3_rows<16, 16>(p, h1, 16, h2);
+  dense3_act<ACT, 16>(h2);
+  p += 16 * 16 + 16;
+  dense3_bias<D>(p + 16 * D, out);
+  dense3_rows<16, D>(p, h2, 16, out);
+  return p + 16 * D + D;
+}
+
+// Frequencies of the sinusoidal embedding by position (q and q + E / 2: 10000^(-q / (E / 2 - 1))), rounded once from
+// fp64 on the host. Computed in fp32 (expf(-step q)) they carry a few 1e-7 of relative error, the same for every
+// layer: harmless for the value, but a time-scale error dt_eff that shows in the derivatives as dt2 * dt_eff.
+struct NvFreq {
+  float w[16];
+};
+
+// Sample i: n_rows == 0: (tv[i * t_stride], xv + i * ld); n_rows > 0 (the sets view of pdeinv_kmv_weights):
+// set = i / n_rows, row r = i % n_rows: (tv[set], xv + set * set_stride + r * ld). Outputs at index i.
+template <int D, int ACT>
+__global__ __launch_bounds__(kBlock, 2) void realnvp_time_kernel(NvpArgs a, NvFreq fr, const float* __restrict__ params,
+                                                              const float* __restrict__ tv, int64_t t_stride,
+                                                              const float* __restrict__ xv, int64_t n, int64_t ld,
+                                                              int64_t n_rows, int64_t set_stride,
+                                                              int64_t layer_stride, float* __restrict__ logp,
+                                                              float* __restrict__ ds) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t set = n_rows > 0 ? i / n_rows : 0;
+  const float t = n_rows > 0 ? tv[set] : tv[i * t_stride];
+  const float* xr = n_rows > 0 ? xv + set * set_stride + (i - set * n_rows) * ld : xv + i * ld;
+  float x[3][D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    x[0][k] = xr[k];
+    x[1][k] = 0.f;
+    x[2][k] = 0.f;
+  }
+  float temb[3][16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) temb[0][q] = temb[1][q] = temb[2][q] = 0.f;
+  const float* p = params;
+  const int E = a.E;
+  if (!a.ignore_time) {
+    if (E > 0) {
+      const int half = E / 2;
+      float se[3][16], h[3][16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {  // position q: sin of frequency q (q < half), cos of frequency q - half
+        se[0][q] = se[1][q] = se[2][q] = 0.f;
+        if (q < E) {
+          const bool is_sin = q < half;
+          const float w = fr.w[q];
+          float sn, cs;
+          sincosf(t * w, &sn, &cs);
+          se[0][q] = is_sin ? sn : cs;
+          se[1][q] = is_sin ? w * cs : -w * sn;
+          se[2][q] = -w * w * se[0][q];
+        }
+      }
+      // two E x E dense layers; unrolled to 16 x 16 with the rows and columns >= E skipped
+      auto layer = [&](const float* W, const float (&in)[3][16], float (&out)[3][16]) {
+#pragma unroll
+        for (int o = 0; o < 16; ++o) {
+          out[0][o] = o < E ? W[E * E + o] : 0.f;
+          out[1][o] = 0.f;
+          out[2][o] = 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          if (q < E) {
+#pragma unroll
+            for (int o = 0; o < 16; ++o) {
+              if (o < E) {
+                const float w = W[q * E + o];
+                out[0][o] = fmaf(in[0][q], w, out[0][o]);
+                out[1][o] = fmaf(in[1][q], w, out[1][o]);
+                out[2][o] = fmaf(in[2][q], w, out[2][o]);
+              }
+            }
+          }
+        }
+      };
+      layer(p, se, h);
+#pragma unroll
+      for (int o = 0; o < 16; ++o) {
+        if (o < E) {
+          float g, g1, g2;
+          nvp_act_d2<ACT>(h[0][o], g, g1, g2);
+          const float z1 = h[1][o];
+          h[0][o] = g;
+          h[2][o] = fmaf(g2 * z1, z1, g1 * h[2][o]);
+          h[1][o] = g1 * z1;
+        }
+      }
+      p += E * E + E;
+      layer(p, h, temb);
+      p += E * E + E;
+    } else {
+      temb[0][0] = t;
+      temb[1][0] = 1.f;
+    }
+  }
+  const float* layers = p;
+  const bool hard = !a.ignore_time && a.soft_init == 0.f;
+  float ldj[3] = {0.f, 0.f, 0.f};
+  for (int l = a.n_layers - 1; l >= 0; --l) {  // likelihood direction: reversed layers
+    const float* lp = layers + (int64_t)l * layer_stride;
+    const float* m = a.masks + l * D;
+    float xm[3][D];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int k = 0; k < D; ++k) xm[s][k] = x[s][k] * m[k];
+    float sc[3][D], tr[3][D];
+    const float* sfp = lp;
+    const int n_t = a.in_dim - D;
+    const float* q = basic_mlp3<D, ACT>(lp + D, xm, temb, n_t, sc);
+    basic_mlp3<D, ACT>(q, xm, temb, n_t, tr);
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const float keep = 1.f - m[k];
+      float s0 = sc[0][k], s1 = sc[1][k], s2 = sc[2][k];
+      float t0 = tr[0][k], t1 = tr[1][k], t2 = tr[2][k];
+      if (hard) {  // (t f)' = f + t f', (t f)'' = 2 f' + t f''
+        s2 = fmaf(t, s2, 2.f * s1);
+        s1 = fmaf(t, s1, s0);
+        s0 *= t;
+        t2 = fmaf(t, t2, 2.f * t1);
+        t1 = fmaf(t, t1, t0);
+        t0 *= t;
+      }
+      // The coupling update itself on the accurate expf / tanhf / division (d per layer, against the nets' hundreds
+      // of activations): the three streams of x are large and every later layer sees their rounding, so an ulp
+      // here is what the derivatives' error is made of.
+      const float sf = expf(sfp[k]);
+      const float th = tanhf(s0 / sf), g1 = 1.f - th * th;
+      // sk = tanh(s / sf) sf keep
+      const float k0 = th * sf * keep;
+      const float k1 = g1 * s1 * keep;
+      const float k2 = g1 * (s2 - 2.f * th * s1 * s1 / sf) * keep;
+      const float e0 = expf(k0), e1 = e0 * k1, e2 = e0 * fmaf(k1, k1, k2);
+      const float y0 = x[0][k] + t0 * keep, y1 = x[1][k] + t1 * keep, y2 = x[2][k] + t2 * keep;
+      x[0][k] = y0 * e0;
+      x[1][k] = fmaf(y1, e0, y0 * e1);
+      x[2][k] = fmaf(y2, e0, fmaf(2.f * y1, e1, y0 * e2));
+      ldj[0] += k0;
+      ldj[1] += k1;
+      ldj[2] += k2;
+    }
+  }
+  // quad = diff^T A diff and its derivatives (A need not be symmetric)
+  float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+      const float w = a.inv_cov[r * D + c];
+      a0 = fmaf(w, x[0][c] - a.mean[c], a0);
+      a1 = fmaf(w, x[1][c], a1);
+      a2 = fmaf(w, x[2][c], a2);
+    }
+    const float d0 = x[0][r] - a.mean[r];
+    q0 = fmaf(d0, a0, q0);
+    q1 = fmaf(x[1][r], a0, fmaf(d0, a1, q1));
+    q2 = fmaf(x[2][r], a0, fmaf(2.f * x[1][r], a1, fmaf(d0, a2, q2)));
+  }
+  if (logp) logp[i] = -0.5f * (a.log_det + q0) + ldj[0];
+  f32x2 o = {fmaf(-0.5f, q1, ldj[1]), fmaf(-0.5f, q2, ldj[2])};
+  if (a.ignore_time) o = f32x2{0.f, 0.f};
+  *reinterpret_cast<f32x2*>(ds + 2 * i) = o;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Matrix-core path of the time derivatives for the reference's flow (celu / elu, packed layout: d <= 4, 4 <= E <= 12,
+// time-conditioned). The tile machinery of realnvp_grad_kernel: 16-sample tiles in the v_mfma_f32_16x16x4_f32
+// accumulator layout, the LDS weight image NvM<true>, layers chained with no data movement. The three Taylor
+// streams are three B operands against one A read (kNvT tiles each: 3 kNvT independent MFMA chains per weight
+// fetch); the activation rule is the epilogue between layers; the coupling update, the base form and the outputs
+// are the general path's arithmetic (accurate expf / tanhf, NvFreq frequencies), one coordinate per lane group.
+// ---------------------------------------------------------------------------------------------
+typedef NvV NvV3[3];
+
+template <int JM = 0xF>
+__device__ __forceinline__ void nv_fwdT3(const float* W, const NvLane& ln, const NvV3& x, NvV3& c) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (!((JM >> j) & 1)) continue;
+    const float av = W[(4 * ln.g + j) * kNvWS + ln.s];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u) c[s][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, x[s][u][j], c[s][u], 0, 0, 0);
+  }
+}
+__device__ __forceinline__ void nv_bias3(NvV3& z, const f32x4& b) {
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    z[0][u] = b;
+    z[1][u] = z[2][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+// celu on the three streams (padding components: z = z' = z'' = 0 -> exactly 0)
+__device__ __forceinline__ void nv_celu3(NvV3& z) {
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float g, g1, g2;
+      nvp_act_d2<PDEINV_ACT_CELU>(z[0][u][c], g, g1, g2);
+      const float z1 = z[1][u][c];
+      z[0][u][c] = g;
+      z[2][u][c] = fmaf(g2 * z1, z1, g1 * z[2][u][c]);
+      z[1][u][c] = g1 * z1;
+    }
+}
+// BasicMLP on the three streams, packed layout: input [xm (register 0) | temb (registers 1..3)]
+__device__ __forceinline__ void nv_mlp_fwd3(const float* p, const NvLane& ln, const NvV3& temb, const float (&xm)[3][kNvT],
+                                            NvV3& out) {
+  using M = NvM<true>;
+  NvV3 in, z, h;
+#pragma unroll
+  for (int s = 0; s < 3; ++s)
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) in[s][u] = f32x4{xm[s][u], temb[s][u][1], temb[s][u][2], temb[s][u][3]};
+  nv_bias3(z, nv_vec(p + M::B0, ln));
+  nv_fwdT3(p + M::W0T, ln, in, z);
+  nv_celu3(z);
+  nv_bias3(h, nv_vec(p + M::B1, ln));
+  nv_fwdT3<0x3>(p + M::W1, ln, z, h);  // h0: 8 units in registers 0, 1
+  nv_celu3(h);
+  nv_bias3(z, nv_vec(p + M::B2, ln));
+  nv_fwdT3(p + M::W2, ln, h, z);
+  nv_celu3(z);
+  nv_bias3(out, nv_vec(p + M::B3, ln));
+  nv_fwdT3(p + M::W3, ln, z, out);
+}
+
+#ifndef PDEINV_NVW_TIME
+#define PDEINV_NVW_TIME 2
+#endif
+__global__ __launch_bounds__(kBlock, PDEINV_NVW_TIME) void realnvp_time_mfma_kernel(
+    NvpArgs a, NvFreq fr, int d, const float* __restrict__ params, const float* __restrict__ tv, int64_t t_stride,
+    const float* __restrict__ xv, int64_t n, int64_t ld, int64_t n_rows, int64_t set_stride, int64_t layer_stride,
+    float* __restrict__ logp, float* __restrict__ ds) {
+  using M = NvM<true>;
+  __shared__ float sW[M::LAYER];  // current coupling layer (padded); the time embedding before the first
+  __shared__ float sF[48];        // sinusoid table: frequency, sin weight, cos weight
+  __shared__ uint32_t sDst[kNvRaw];
+  const int E = a.E, n_t = a.in_dim - d;
+  const float* layers = params + 2 * ((int64_t)E * E + E);
+  const bool hard = a.soft_init == 0.f;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  NvLane ln;
+  {
+    int lane = tid & 63;
+    asm volatile("" : "+v"(lane));
+    ln.g = lane >> 4;
+    ln.s = lane & 15;
+    ln.sw = ln.sr = 0;
+  }
+  auto put_mat = [&](float* dst, const float* src, int ld_src, auto rm, auto cm) {
+    for (int q = tid; q < 16 * kNvWS; q += kBlock) {
+      const int r = q / kNvWS, c = q - r * kNvWS;
+      const int sr = c < 16 ? rm(r) : -1, sc = c < 16 ? cm(c) : -1;
+      dst[q] = (sr >= 0 && sc >= 0) ? src[sr * ld_src + sc] : 0.f;
+    }
+  };
+  auto put_vec = [&](float* dst, const float* src, auto m) {
+    for (int q = tid; q < 16; q += kBlock) {
+      const int k = m(q);
+      dst[q] = k >= 0 ? src[k] : 0.f;
+    }
+  };
+  auto idn = [E](int p) { return p < E ? p : -1; };
+  auto tmap = [E](int p) { return nv_tinv<true>(p, E); };
+  if (tid < 16) {
+    const bool on = tid < E, is_sin = tid < E / 2;
+    sF[tid] = on ? fr.w[tid] : 0.f;
+    sF[16 + tid] = on && is_sin ? 1.f : 0.f;
+    sF[32 + tid] = on && !is_sin ? 1.f : 0.f;
+  }
+  for (int k = tid; k < layer_stride; k += kBlock) sDst[k] = nv_layer_dst<true>(k, d, n_t);
+  for (int q = tid; q < M::LAYER; q += kBlock) sW[q] = 0.f;  // padding: never written by a layer
+  __syncthreads();
+  put_mat(sW + M::E_W1, params, E, idn, idn);
+  put_vec(sW + M::E_B1, params + E * E, idn);
+  put_mat(sW + M::E_W2, params + E * E + E, E, idn, tmap);  // temb at its positions
+  put_vec(sW + M::E_B2, params + 2 * E * E + E, tmap);
+  __syncthreads();
+  // ---- the wave's tiles: lane (g, s) holds coordinate g of sample s ----
+  float xs[3][kNvT], tt[kNvT], ldj[3][kNvT];
+  int64_t idx[kNvT];
+  const int64_t base = (int64_t)blockIdx.x * kNvSPB + wave * 16 * kNvT;
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    const int64_t i = base + 16 * u + ln.s;
+    idx[u] = i < n ? i : -1;
+    float t = 0.f, x0 = 0.f;
+    if (i < n) {
+      const int64_t set = n_rows > 0 ? i / n_rows : 0;
+      t = n_rows > 0 ? tv[set] : tv[i * t_stride];
+      const float* xr = n_rows > 0 ? xv + set * set_stride + (i - set * n_rows) * ld : xv + i * ld;
+      if (ln.g < d) x0 = xr[ln.g];
+    }
+    tt[u] = t;
+    xs[0][u] = x0;
+    xs[1][u] = xs[2][u] = 0.f;
+    ldj[0][u] = ldj[1][u] = ldj[2][u] = 0.f;
+  }
+  NvV3 temb;
+  {
+    NvV3 se, he;
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int q = 4 * ln.g + c;
+        const float w = sF[q], ws = sF[16 + q], wc = sF[32 + q];
+        float sn, cs;
+        sincosf(tt[u] * w, &sn, &cs);
+        const float v0 = ws * sn + wc * cs;
+        se[0][u][c] = v0;
+        se[1][u][c] = w * (ws * cs - wc * sn);
+        se[2][u][c] = -w * w * v0;
+      }
+    nv_bias3(he, nv_vec(sW + M::E_B1, ln));
+    nv_fwdT3(sW + M::E_W1, ln, se, he);
+    nv_celu3(he);
+    nv_bias3(temb, nv_vec(sW + M::E_B2, ln));
+    nv_fwdT3(sW + M::E_W2, ln, he, temb);
+  }
+  __syncthreads();  // every wave has read the time embedding: back to the zero-padded layer image
+  for (int q = tid; q < M::TEMB; q += kBlock) sW[q] = 0.f;
+  for (int l = a.n_layers - 1; l >= 0; --l) {  // likelihood direction
+    __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
+    const float* lp = layers + (int64_t)l * layer_stride;
+    for (int k = tid; k < layer_stride; k += kBlock) sW[sDst[k] & 0xFFFFu] = lp[k];
+    if (tid < 16) {  // the layer's mask by position, padded with 1
+      const int k = nv_xinv<true>(tid, d);
+      sW[M::MASK + tid] = k >= 0 ? a.masks[l * d + k] : 1.f;
+    }
+    __syncthreads();
+    const float m = sW[M::MASK + 4 * ln.g], keep = 1.f - m;
+    const float sf = expf(sW[M::SF + 4 * ln.g]);
+    float xm[3][kNvT];
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u) xm[s][u] = xs[s][u] * m;
+    NvV3 so, to;
+    nv_mlp_fwd3(sW + M::SNET, ln, temb, xm, so);
+    nv_mlp_fwd3(sW + M::TNET, ln, temb, xm, to);
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+      const float t = tt[u];
+      float s0 = so[0][u][0], s1 = so[1][u][0], s2 = so[2][u][0];
+      float t0 = to[0][u][0], t1 = to[1][u][0], t2 = to[2][u][0];
+      if (hard) {
+        s2 = fmaf(t, s2, 2.f * s1);
+        s1 = fmaf(t, s1, s0);
+        s0 *= t;
+        t2 = fmaf(t, t2, 2.f * t1);
+        t1 = fmaf(t, t1, t0);
+        t0 *= t;
+      }
+      const float th = tanhf(s0 / sf), g1 = 1.f - th * th;
+      const float k0 = th * sf * keep;
+      const float k1 = g1 * s1 * keep;
+      const float k2 = g1 * (s2 - 2.f * th * s1 * s1 / sf) * keep;
+      const float e0 = expf(k0), e1 = e0 * k1, e2 = e0 * fmaf(k1, k1, k2);
+      const float y0 = xs[0][u] + t0 * keep, y1 = xs[1][u] + t1 * keep, y2 = xs[2][u] + t2 * keep;
+      xs[0][u] = y0 * e0;
+      xs[1][u] = fmaf(y1, e0, y0 * e1);
+      xs[2][u] = fmaf(y2, e0, fmaf(2.f * y1, e1, y0 * e2));
+      ldj[0][u] += k0;
+      ldj[1][u] += k1;
+      ldj[2][u] += k2;
+    }
+  }
+  // ---- base density: every lane gathers its sample's coordinates (lane 16 c + s holds coordinate c) ----
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    float xc[3][4], lj[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xc[s][c] = __shfl(xs[s][u], 16 * c + ln.s, 64);
+      float v = ldj[s][u];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      lj[s] = v;
+    }
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (r < d) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (c < d) {
+            const float w = a.inv_cov[r * d + c];
+            a0 = fmaf(w, xc[0][c] - a.mean[c], a0);
+            a1 = fmaf(w, xc[1][c], a1);
+            a2 = fmaf(w, xc[2][c], a2);
+          }
+        }
+        const float d0 = xc[0][r] - a.mean[r];
+        q0 = fmaf(d0, a0, q0);
+        q1 = fmaf(xc[1][r], a0, fmaf(d0, a1, q1));
+        q2 = fmaf(xc[2][r], a0, fmaf(2.f * xc[1][r], a1, fmaf(d0, a2, q2)));
+      }
+    }
+    const int64_t i = idx[u];
+    if (ln.g == 0 && i >= 0) {
+      if (logp) logp[i] = -0.5f * (a.log_det + q0) + lj[0];
+      *reinterpret_cast<f32x2*>(ds + 2 * i) = f32x2{fmaf(-0.5f, q1, lj[1]), fmaf(-0.5f, q2, lj[2])};
     }
   }
 }
@@ -1161,4 +1703,102 @@ extern "C" int pdeinv_realnvp_value_and_grad(const pdeinv_realnvp_desc* d, const
     if (rc) return rc;
   }
   return PDEINV_OK;
+}
+
+// Path selector of the time-derivative entry points (tests and tools/nvp_time_bench.py): 0 = AUTO, 1 = the general
+// per-thread path, 2 = the matrix-core path (UNSUPPORTED outside its envelope). Process-wide.
+static int g_nvp_time_impl = 0;
+static bool nvp_time_mfma_ok(const pdeinv_realnvp_desc* d) {
+  return (d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU) && d->dim <= 4 && !d->ignore_time &&
+         d->embed_time_dim >= 4 && d->embed_time_dim <= 12;
+}
+// AUTO takes the matrix-core path only where it measured faster than the general path.
+static bool nvp_time_auto_mfma(const pdeinv_realnvp_desc* d) { return PDEINV_NVP_TIME_AUTO_MFMA && nvp_time_mfma_ok(d); }
+
+// Shared by the two time-derivative entry points: n_rows == 0 is the per-sample view (t_stride), n_rows > 0 the
+// sets view (realnvp_time_kernel).
+static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, const float* t, int64_t t_stride,
+                           const float* x, int64_t n, int64_t ld, int64_t n_rows, int64_t set_stride, float* logp,
+                           float* ds, void* stream) {
+  PDEINV_REQUIRE(d != nullptr, PDEINV_ERR_INVALID, "realnvp_time_derivs: null descriptor");
+  PDEINV_REQUIRE(d->dim >= 1 && d->dim <= 8, PDEINV_ERR_UNSUPPORTED, "realnvp_time_derivs: dim must be in [1, 8]");
+  PDEINV_REQUIRE(d->n_layers >= 1 && d->n_layers <= PDEINV_REALNVP_MAX_LAYERS, PDEINV_ERR_UNSUPPORTED,
+                 "realnvp_time_derivs: 1 <= n_layers <= 64");
+  PDEINV_REQUIRE(d->embed_time_dim >= 0 && d->embed_time_dim <= 16 && d->embed_time_dim % 2 == 0 &&
+                     d->embed_time_dim != 2,
+                 PDEINV_ERR_UNSUPPORTED, "realnvp_time_derivs: embed_time_dim must be 0 or even in [4, 16]");
+  PDEINV_REQUIRE(d->activation >= PDEINV_ACT_CELU && d->activation <= PDEINV_ACT_GELU, PDEINV_ERR_UNSUPPORTED,
+                 "realnvp_time_derivs: unknown activation");
+  PDEINV_REQUIRE(d->masks && d->base_mean && d->base_inv_cov, PDEINV_ERR_INVALID,
+                 "realnvp_time_derivs: null host array");
+  PDEINV_REQUIRE(n >= 0 && ld >= d->dim && t_stride >= 0 && set_stride >= 0, PDEINV_ERR_INVALID,
+                 "realnvp_time_derivs: bad sizes");
+  PDEINV_REQUIRE(n <= (int64_t)0x7FFFFFFF * kBlock, PDEINV_ERR_INVALID, "realnvp_time_derivs: too many samples");
+  if (n == 0) return PDEINV_OK;
+  PDEINV_REQUIRE(params && t && x && ds, PDEINV_ERR_INVALID, "realnvp_time_derivs: null device pointer");
+  PDEINV_REQUIRE(((uintptr_t)ds & 7) == 0 && ((uintptr_t)params & 3) == 0 && ((uintptr_t)t & 3) == 0 &&
+                     ((uintptr_t)x & 3) == 0 && ((uintptr_t)logp & 3) == 0,
+                 PDEINV_ERR_INVALID, "realnvp_time_derivs: misaligned pointer (d_ds needs 8 bytes, the others 4)");
+  const int D = d->dim;
+  NvpArgs a{};
+  a.n_layers = d->n_layers;
+  a.ignore_time = d->ignore_time ? 1 : 0;
+  a.E = a.ignore_time ? 0 : d->embed_time_dim;
+  a.in_dim = in_dim_of(d);
+  a.act = d->activation;
+  a.soft_init = d->soft_init;
+  a.log_det = d->base_log_det;
+  for (int k = 0; k < D; ++k) a.mean[k] = d->base_mean[k];
+  for (int k = 0; k < D * D; ++k) a.inv_cov[k] = d->base_inv_cov[k];
+  for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
+  NvFreq fr{};
+  for (int q = 0; q < a.E; ++q)
+    fr.w[q] = (float)exp(-(log(10000.0) / (double)(a.E / 2 - 1)) * (double)(q % (a.E / 2)));
+  const int64_t ls = layer_params(D, a.in_dim);
+  hipStream_t st = (hipStream_t)stream;
+  PDEINV_REQUIRE(g_nvp_time_impl != 2 || nvp_time_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,
+                 "realnvp_time_derivs: the matrix-core path takes celu / elu, dim <= 4, 4 <= E <= 12, no ignore_time");
+  if (g_nvp_time_impl == 2 || (g_nvp_time_impl == 0 && nvp_time_auto_mfma(d))) {
+    hipLaunchKernelGGL(realnvp_time_mfma_kernel, dim3(grid_for(n, kNvSPB)), dim3(kBlock), 0, st, a, fr, D, params, t,
+                       t_stride, x, n, ld, n_rows, set_stride, ls, logp, ds);
+    return check_launch("realnvp_time_mfma_kernel");
+  }
+  const dim3 g(grid_for(n));
+  // one instantiation per (dim, activation); celu and elu (alpha = 1) are the same map
+#define CASE(DD, AA) case DD: hipLaunchKernelGGL((realnvp_time_kernel<DD, AA>), g, dim3(kBlock), 0, st, a, fr, params, t, t_stride, x, n, ld, n_rows, set_stride, ls, logp, ds); break;
+#define DIMS(AA) switch (D) { CASE(1, AA) CASE(2, AA) CASE(3, AA) CASE(4, AA) CASE(5, AA) CASE(6, AA) CASE(7, AA) CASE(8, AA) }
+  switch (a.act) {
+    case PDEINV_ACT_CELU: case PDEINV_ACT_ELU: DIMS(PDEINV_ACT_CELU) break;
+    case PDEINV_ACT_RELU: DIMS(PDEINV_ACT_RELU) break;
+    case PDEINV_ACT_TANH: DIMS(PDEINV_ACT_TANH) break;
+    case PDEINV_ACT_SILU: DIMS(PDEINV_ACT_SILU) break;
+    case PDEINV_ACT_SOFTPLUS: DIMS(PDEINV_ACT_SOFTPLUS) break;
+    default: DIMS(PDEINV_ACT_GELU) break;
+  }
+#undef DIMS
+#undef CASE
+  return check_launch("realnvp_time_kernel");
+}
+
+extern "C" int pdeinv_realnvp_time_derivs(const pdeinv_realnvp_desc* d, const float* params, const float* t,
+                                          int64_t t_stride, const float* x, int64_t n, int64_t ld, float* logp,
+                                          float* ds, void* stream) {
+  return nvp_time_launch(d, params, t, t_stride, x, n, ld, 0, 0, logp, ds, stream);
+}
+
+extern "C" int pdeinv_realnvp_time_derivs_sets(const pdeinv_realnvp_desc* d, const float* params, const float* tau,
+                                               const float* z, int64_t n_sets, int64_t n_rows, int64_t set_stride,
+                                               int64_t ld, float* logp, float* ds, void* stream) {
+  PDEINV_REQUIRE(n_sets >= 0 && n_rows >= 0, PDEINV_ERR_INVALID, "realnvp_time_derivs_sets: negative sizes");
+  PDEINV_REQUIRE(n_sets == 0 || n_rows <= INT64_MAX / n_sets, PDEINV_ERR_INVALID,
+                 "realnvp_time_derivs_sets: n_sets * n_rows overflows");
+  if (d && ld == 0) ld = 2 * (int64_t)d->dim;  // rows [x | v], as pdeinv_kmv_weights
+  return nvp_time_launch(d, params, tau, 1, z, n_sets * n_rows, ld, n_rows, set_stride, logp, ds, stream);
+}
+
+extern "C" int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* d, int32_t impl) {
+  if (impl >= 0 && impl <= 2) g_nvp_time_impl = impl;
+  if (!d) return g_nvp_time_impl;
+  if (g_nvp_time_impl == 2) return nvp_time_mfma_ok(d) ? 1 : PDEINV_ERR_UNSUPPORTED;
+  return g_nvp_time_impl == 0 && nvp_time_auto_mfma(d) ? 1 : 0;
 }

@@ -69,6 +69,8 @@ def dlogrho_coefficients(s_values, configuration, dim: int) -> np.ndarray:
 
 
 class KineticMcKeanVlasov(KineticFokkerPlanck):
+    learned_log_density = None  # see use_learned_log_density
+
     def __init__(self, cfg, rng: Key):
         super().__init__(cfg, rng)
         self.interaction = MeanFieldQuadraticPotential(self.initial_configuration["tilde_F"])
@@ -76,6 +78,16 @@ class KineticMcKeanVlasov(KineticFokkerPlanck):
     def coefficients(self, s_values, device="cuda") -> torch.Tensor:
         c = dlogrho_coefficients(s_values, self.initial_configuration, self.dim)
         return torch.as_tensor(c, dtype=torch.float32, device=device).contiguous()
+
+    def use_learned_log_density(self, log_density_fn):
+        """Attach (or, with None, detach) a learned X-marginal, the function core.log_density_estimation
+        .estimate_log_density returns (it carries .model, .params and .partial_s): the KMV residual then takes
+        ds log rho and ds2 log rho from the flow (pdeinv_realnvp_time_derivs_sets) instead of the closed-form
+        Gaussian marginal of `coefficients`. With nothing attached every path is what it was."""
+        if log_density_fn is not None and not all(hasattr(log_density_fn, a) for a in ("model", "params", "partial_s")):
+            raise TypeError("use_learned_log_density: expected the log_density_fn of estimate_log_density "
+                            "(with .model, .params and .partial_s)")
+        self.learned_log_density = log_density_fn
 
     def _ds(self, s, x: torch.Tensor):
         s_arr = np.atleast_1d(np.asarray(s, dtype=np.float64))

@@ -42,8 +42,23 @@ def layout(data: dict, d: int):
     return z, n_sets, n_rows, 2 * d, n_sets * 2 * d, tau
 
 
+def learned_ds(learned, z, n_sets, n_rows, set_stride, ld, tau):
+    """(ds log rho, ds2 log rho) [n_sets, n_rows, 2] of an attached learned density (pde_instance
+    .use_learned_log_density) over the layout() view: one pass of pdeinv_realnvp_time_derivs_sets."""
+    flow, flat = learned.model, learned.params
+    flat = flat["params"] if isinstance(flat, dict) else flat
+    tau_dev = torch.as_tensor(tau, dtype=torch.float32, device=z.device).contiguous()
+    return native.realnvp_time_derivs_sets(flow._desc, flat, tau_dev, z, n_sets, n_rows, set_stride, ld)[1]
+
+
 def value_and_grad_fn(forward_fn, params, data, rng, pde_instance):
     model = resolve_model(forward_fn)
+    learned = getattr(pde_instance, "learned_log_density", None)
+    if learned is not None and "kmv_sums" in data:
+        raise ValueError('data["kmv_sums"] (the per-stamp sums formed inside the simulator from the analytic '
+                         "Gaussian coefficients) cannot be combined with a learned log-density "
+                         "(pde_instance.use_learned_log_density): pass the rows (\"0T_tm\" / \"0T\") instead, or "
+                         "detach the learned density")
     if model.residual_kind == "mlp":
         return _value_and_grad_mlp(model, params, data, pde_instance)
     if model.residual_kind != "quadratic":
@@ -52,6 +67,11 @@ def value_and_grad_fn(forward_fn, params, data, rng, pde_instance):
     gamma = float(pde_instance.initial_configuration["gamma_friction"])
     if "kmv_sums" in data:  # formed inside the McKean-Vlasov simulator (pdeinv_sde_simulate_mf_kmv)
         mom, wst = data["kmv_sums"]
+    elif learned is not None:  # ds from the flow, then the two sets of sums
+        z, n_sets, n_rows, set_stride, ld, tau = layout(data, d)
+        ds = learned_ds(learned, z, n_sets, n_rows, set_stride, ld, tau)
+        mom = native.moments_batched(z, n_sets, n_rows, 2 * d, set_stride, ld)
+        wst = native.kmv_weights_from_ds(d, gamma, ds, z, n_sets, n_rows, set_stride, ld)
     else:
         z, n_sets, n_rows, set_stride, ld, tau = layout(data, d)
         coef = pde_instance.coefficients(tau, z.device)
@@ -88,8 +108,12 @@ def _value_and_grad_mlp(model, params, data, pde_instance):
     d = pde_instance.dim
     gamma = float(pde_instance.initial_configuration["gamma_friction"])
     z, n_sets, n_rows, set_stride, ld, tau = layout(data, d)
-    coef = pde_instance.coefficients(tau, z.device)
-    _, ds = native.kmv_weights(d, gamma, coef, z, n_sets, n_rows, set_stride, ld, want_ds=True)
+    learned = getattr(pde_instance, "learned_log_density", None)
+    if learned is not None:
+        ds = learned_ds(learned, z, n_sets, n_rows, set_stride, ld, tau)
+    else:
+        coef = pde_instance.coefficients(tau, z.device)
+        _, ds = native.kmv_weights(d, gamma, coef, z, n_sets, n_rows, set_stride, ld, want_ds=True)
     flat = model.flat(params)
     acc, grad = native.residual_kmv_mlp(model.dims(d), flat, z, n_sets, n_rows, set_stride, ld, ds,
                                         pde_instance.initial_configuration["tilde_F"], gamma)

@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "pdeinv_kmv_moments_weights_mf_sums_workspace_bytes", "pdeinv_kmv_moments_weights_mf_sums",
     "pdeinv_sde_simulate_kfp_gmm_workspace_bytes", "pdeinv_sde_simulate_kfp_gmm",
     "pdeinv_sde_simulate_mf_next_workspace_bytes", "pdeinv_sde_simulate_mf_next", "pdeinv_ou_exact_sample",
+    "pdeinv_realnvp_time_derivs", "pdeinv_realnvp_time_derivs_sets", "pdeinv_realnvp_time_impl",
+    "pdeinv_kmv_weights_from_ds_workspace_bytes", "pdeinv_kmv_weights_from_ds",
 )
 
 
@@ -203,6 +205,11 @@ def lib():
         "pdeinv_adam_update": (i32, [P, P, P, P, i64, f32, f32, f32, f32, f32, i32, P]),
         "pdeinv_realnvp_param_count": (i64, [P]),
         "pdeinv_realnvp_logdensity": (i32, [P, P, P, i64, P, i64, i64, P, P]),
+        "pdeinv_realnvp_time_derivs": (i32, [P, P, P, i64, P, i64, i64, P, P, P]),
+        "pdeinv_realnvp_time_derivs_sets": (i32, [P, P, P, P, i64, i64, i64, i64, P, P, P]),
+        "pdeinv_realnvp_time_impl": (i32, [P, i32]),
+        "pdeinv_kmv_weights_from_ds_workspace_bytes": (ctypes.c_size_t, [i64, i64, i32]),
+        "pdeinv_kmv_weights_from_ds": (i32, [i32, f32, P, P, i64, i64, i64, i64, P, P, P]),
         "pdeinv_realnvp_grad_workspace": (i64, [P, i64]),
         "pdeinv_realnvp_value_and_grad": (i32, [P, P, P, i64, P, i64, i64, P, P, P, i64, P]),
         "pdeinv_residual_kfp_mlp_workspace_bytes": (ctypes.c_size_t, [P]),
@@ -1049,6 +1056,91 @@ def realnvp_logdensity(desc, params: torch.Tensor, t: torch.Tensor, x: torch.Ten
     _check(lib().pdeinv_realnvp_logdensity(ctypes.byref(desc), _dev(params, "params"), _dev(t, "t"),
                                            0 if t.numel() == 1 else 1, px, n, ld, _dev(out, "out"),
                                            stream_handle()), "pdeinv_realnvp_logdensity")
+    return out
+
+
+NVP_TIME_AUTO, NVP_TIME_GENERAL, NVP_TIME_MATRIX = 0, 1, 2
+NVP_TIME_PATHS = {0: "general", 1: "matrix_core"}
+
+
+def realnvp_time_impl(desc, impl: int = -1) -> str:
+    """Select the path of realnvp_time_derivs(_sets) for tests and measurements (process-wide: NVP_TIME_AUTO /
+    GENERAL / MATRIX; -1 only asks) and name the path `desc` takes now (pdeinv_realnvp_time_impl)."""
+    p = int(lib().pdeinv_realnvp_time_impl(ctypes.byref(desc), int(impl)))
+    if p < 0:
+        raise NotImplementedError("RealNVP time derivatives: the matrix-core path does not take this flow")
+    return NVP_TIME_PATHS[p]
+
+
+def _time_derivs_params(desc, params: torch.Tensor) -> None:
+    """The flat-parameter check of the time-derivative calls; a descriptor outside the envelope (no parameter
+    count) is left to the library, which names what is unsupported."""
+    P = int(lib().pdeinv_realnvp_param_count(ctypes.byref(desc)))
+    if not params.is_contiguous() or (P >= 0 and params.numel() != P):
+        raise ValueError("RealNVP: params must be a contiguous flat vector of pdeinv_realnvp_param_count floats")
+
+
+def realnvp_time_derivs(desc, params: torch.Tensor, t: torch.Tensor, x: torch.Tensor, ds: Optional[torch.Tensor] = None):
+    """(log p_t(x) [n], ds [n, 2] = (d/dt, d2/dt2) of it) for rows x [n, dim] and times t [n] (or a single t,
+    broadcast), in one pass of second-order forward mode in t (pdeinv_realnvp_time_derivs). `ds`: an output
+    buffer to fill (contiguous fp32 [n, 2])."""
+    _require_gpu()
+    n = x.shape[0]
+    _time_derivs_params(desc, params)
+    t = t.reshape(-1)
+    if t.numel() not in (1, n):
+        raise ValueError("RealNVP: t must have one entry per row or a single entry")
+    px, _, ld = _rows(x, "x", desc.dim)
+    if ds is None:
+        ds = torch.empty((n, 2), device=x.device, dtype=torch.float32)
+    elif tuple(ds.shape) != (n, 2) or not ds.is_contiguous():
+        raise ValueError(f"RealNVP: ds must be contiguous [{n}, 2]")
+    logp = torch.empty(n, device=x.device, dtype=torch.float32)
+    t = t.contiguous()
+    _check(lib().pdeinv_realnvp_time_derivs(ctypes.byref(desc), _dev(params, "params"), _dev(t, "t"),
+                                            0 if t.numel() == 1 else 1, px, n, ld, _dev(logp, "logp"),
+                                            _dev(ds, "ds"), stream_handle()), "pdeinv_realnvp_time_derivs")
+    return logp, ds
+
+
+def realnvp_time_derivs_sets(desc, params: torch.Tensor, tau: torch.Tensor, z: torch.Tensor, n_sets: int, n_rows: int,
+                             set_stride: int, ld: int, ds: Optional[torch.Tensor] = None):
+    """realnvp_time_derivs over the (z, n_sets, n_rows, set_stride, ld) view of kmv_weights / residual_kmv_mlp: the
+    rows of stamp s are x = z[s * set_stride + r * ld : + dim] and share tau[s]. Returns (logp [n_sets, n_rows],
+    ds [n_sets, n_rows, 2]) — ds in the layout residual_kmv_mlp and kmv_weights_from_ds consume."""
+    _require_gpu()
+    _time_derivs_params(desc, params)
+    tau = tau.reshape(-1)
+    if tau.numel() != n_sets or not tau.is_contiguous():
+        raise ValueError(f"RealNVP: tau must hold one time per set ({n_sets})")
+    if n_sets > 0:
+        _set_view(z, n_sets, n_rows, set_stride, ld, desc.dim)
+    if ds is None:
+        ds = torch.empty((n_sets, n_rows, 2), device=z.device, dtype=torch.float32)
+    elif tuple(ds.shape) != (n_sets, n_rows, 2) or not ds.is_contiguous():
+        raise ValueError(f"RealNVP: ds must be contiguous [{n_sets}, {n_rows}, 2]")
+    logp = torch.empty((n_sets, n_rows), device=z.device, dtype=torch.float32)
+    _check(lib().pdeinv_realnvp_time_derivs_sets(ctypes.byref(desc), _dev(params, "params"), _dev(tau, "tau"),
+                                                 _dev(z, "z"), int(n_sets), int(n_rows), int(set_stride), int(ld),
+                                                 _dev(logp, "logp"), _dev(ds, "ds"), stream_handle()),
+           "pdeinv_realnvp_time_derivs_sets")
+    return logp, ds
+
+
+def kmv_weights_from_ds(d: int, gamma: float, ds: torch.Tensor, z: torch.Tensor, n_sets: int, n_rows: int,
+                        set_stride: int, ld: int) -> torch.Tensor:
+    """The reduction half of kmv_weights with the per-particle (ds log rho, ds2 log rho) [n_sets, n_rows, 2] given:
+    per stamp [sum c, sum c x, sum c x x^T] fp64, c = ds2 + ds^2 + gamma ds — the `wst` of residual_kmv."""
+    _require_gpu()
+    if tuple(ds.shape) != (n_sets, n_rows, 2) or not ds.is_contiguous():
+        raise ValueError(f"kmv_weights_from_ds: ds must be contiguous [{n_sets}, {n_rows}, 2]")
+    _set_view(z, n_sets, n_rows, set_stride, ld, d)
+    nbytes = lib().pdeinv_kmv_weights_from_ds_workspace_bytes(n_sets, n_rows, d)
+    ws = torch.empty(max(nbytes // 4, 1), device=z.device, dtype=torch.float32)
+    out = torch.empty((n_sets, moment_len(d)), device=z.device, dtype=torch.float64)
+    _check(lib().pdeinv_kmv_weights_from_ds(d, float(gamma), _dev(ds, "ds"), _dev(z, "z"), n_sets, n_rows, set_stride,
+                                            ld, _dev(ws, "ws"), _dev(out, "out", torch.float64), stream_handle()),
+           "pdeinv_kmv_weights_from_ds")
     return out
 
 
