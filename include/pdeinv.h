@@ -310,7 +310,7 @@ int pdeinv_moments_batched(const float* d_z, int64_t n_sets, int64_t n_rows, int
  *   [m1 (d), a1, beta1 (d), Gamma1 (d*d), a2, beta2 (d), Gamma2 (d*d)]   (PDEINV_KMV_NCOEF(d))
  * with  ds log rho  = a1 + beta1 . r + r^T Gamma1 r,  ds2 log rho = a2 + beta2 . r + r^T Gamma2 r,
  * r = m1 - x. Per particle the kernel evaluates both, c = ds2 + ds^2 + gamma ds (the weight
- * of the Phi term, kinetic_mckean_vlasov.py:243-248), and accumulates per time stamp the
+ * of the Phi term, kinetic_mckean_vlasov.py:86-91), and accumulates per time stamp the
  * fp64 vector [sum c, sum c x (d), sum c x_i x_j (i<=j)] (pdeinv_moment_len(d) doubles).
  * Optional per-particle output d_ds [n_sets, n_rows, 2] = (ds log rho, ds2 log rho).
  * --------------------------------------------------------------------------------------- */

@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <string>
 
@@ -16,21 +15,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kBlock = 256;          // 4 waves of 64
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-// ---- A/B switches of the measurement tools ------------------------------------------------
-// Only a tools/build_var.sh build with -DPDEINV_AB_ENV=1 reads them: the default library reads no environment
-// variable, so a stray variable in a user's shell cannot change which kernels run.
-#ifndef PDEINV_AB_ENV
-#define PDEINV_AB_ENV 0
-#endif
-inline const char* ab_env(const char* name) {
-#if PDEINV_AB_ENV
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
 
 // ---- error plumbing (host) ------------------------------------------------------------
 void set_error(const std::string& msg);
@@ -460,8 +444,26 @@ struct MlpPadMap {
     }
     return -1;
   }
+  int64_t padded_count() const { return poff[L] + (int64_t)pin[L] * pout[L] + pout[L]; }
 };
 
+// the map of dim -> width x L -> out zero-padded to pdim -> pwidth x L -> pout
+inline MlpPadMap mlp_pad_map(int dim, int width, int L, int out, int pdim, int pwidth, int pout) {
+  MlpPadMap pm{};
+  pm.L = L;
+  int64_t ro = 0, po = 0;
+  for (int l = 0; l <= L; ++l) {
+    pm.din[l] = l == 0 ? dim : width;
+    pm.dout[l] = l == L ? out : width;
+    pm.pin[l] = l == 0 ? pdim : pwidth;
+    pm.pout[l] = l == L ? pout : pwidth;
+    pm.roff[l] = ro;
+    pm.poff[l] = po;
+    ro += (int64_t)pm.din[l] * pm.dout[l] + pm.dout[l];
+    po += (int64_t)pm.pin[l] * pm.pout[l] + pm.pout[l];
+  }
+  return pm;
+}
 
 // fp64 column reducer launched after any kernel that wrote a partial slab.
 void launch_slab_reduce(const float* partials, int n_blocks, int n_cols, double* out,

@@ -7,7 +7,6 @@
 // stamp's moments, so the O(n^2) tensor becomes two streaming passes (moments, weights)
 // plus an O(n_time d^3) finalize — exact, not an approximation.
 #include <math.h>
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -15,16 +14,8 @@ namespace pdeinv {
 
 constexpr int kBatchedGridTarget = 4096;  // C4 KMV pass: r02 2.88 ms at 2048, 2.785 at 3072; r04 (buffer loads) 2.52 at 3072, 2.486 at 4096, 2.51 at 6144 (profiles/r04_kmv_grid_ab.txt)
 
-static int64_t grid_target() {
-  static const int64_t t = [] {
-    const char* e = ab_env("PDEINV_KMV_GRID");  // A/B experiments (tools)
-    return e ? (int64_t)atol(e) : (int64_t)kBatchedGridTarget;
-  }();
-  return t;
-}
-
 static int batched_bx(int64_t n_sets, int64_t n_rows) {
-  int64_t bx = (grid_target() + n_sets - 1) / (n_sets > 0 ? n_sets : 1);
+  int64_t bx = (kBatchedGridTarget + n_sets - 1) / (n_sets > 0 ? n_sets : 1);
   const int64_t need = (n_rows + kBlock - 1) / kBlock;
   if (bx > need) bx = need;
   if (bx < 1) bx = 1;
@@ -98,7 +89,7 @@ __global__ __launch_bounds__(kBlock) void kmv_weights_kernel(float gamma, const 
       o[0] = q1;
       o[1] = q2;
     }
-    const float w = q2 + q1 * q1 + gamma * q1;  // kinetic_mckean_vlasov.py:243-248
+    const float w = q2 + q1 * q1 + gamma * q1;  // kinetic_mckean_vlasov.py:86-91
     acc.add(x, w);
   }
   __shared__ float lds[kWavesPerBlock * moment_len(D)];
@@ -126,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void kmv_weights_from_ds_kernel(float gamma
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = row[k];
     const f32x2 q = dst[r];
-    const float w = q[1] + q[0] * q[0] + gamma * q[0];  // kinetic_mckean_vlasov.py:243-248
+    const float w = q[1] + q[0] * q[0] + gamma * q[0];  // kinetic_mckean_vlasov.py:86-91
     acc.add(x, w);
   }
   __shared__ float lds[kWavesPerBlock * moment_len(D)];
@@ -267,7 +258,7 @@ __global__ __launch_bounds__(kBlock) void kmv_moments_weights_kernel(float gamma
       for (int j = i; j < D; ++j, ++o) g = cpair[o] * f32x2{rr[j], rr[j]} + g;
       q = g * f32x2{rr[i], rr[i]} + q;
     }
-    const float w = active ? q[1] + q[0] * q[0] + gamma * q[0] : 0.f;  // kinetic_mckean_vlasov.py:243-248
+    const float w = active ? q[1] + q[0] * q[0] + gamma * q[0] : 0.f;  // kinetic_mckean_vlasov.py:86-91
     acc.add(v, w);
     if constexpr (MF) {  // the next simulate's update-t normals of this lane's particle
       if (active) {

@@ -514,34 +514,8 @@ extern "C" int pdeinv_mlp_fused_supported(int32_t dim, int32_t n_layers, int32_t
   return fused_shape(&d) ? 1 : 0;
 }
 
-// PDEINV_MLP_FIRST_ORDER=0 (A/B): the boundary sets take the full second-order chain as the 0T set does
-static bool first_order_enabled() {
-  static const bool on = [] {
-    const char* e = ab_env("PDEINV_MLP_FIRST_ORDER");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
 static MlpPadMap width_pad_map(const pdeinv_kfp_mlp_desc* d, const FusedShape& f) {
-  MlpPadMap pm{};
-  pm.L = d->n_layers;
-  int64_t ro = 0, po = 0;
-  for (int l = 0; l <= pm.L; ++l) {
-    pm.din[l] = l == 0 ? d->dim : d->width;
-    pm.dout[l] = l == pm.L ? d->out_features : d->width;
-    pm.pin[l] = l == 0 ? f.Dp : f.Wp;
-    pm.pout[l] = l == pm.L ? d->out_features : f.Wp;
-    pm.roff[l] = ro;
-    pm.poff[l] = po;
-    ro += (int64_t)pm.din[l] * pm.dout[l] + pm.dout[l];
-    po += (int64_t)pm.pin[l] * pm.pout[l] + pm.pout[l];
-  }
-  return pm;
-}
-
-static int64_t pad_param_count(const MlpPadMap& pm) {
-  return pm.poff[pm.L] + (int64_t)pm.pin[pm.L] * pm.pout[pm.L] + pm.pout[pm.L];
+  return mlp_pad_map(d->dim, d->width, d->n_layers, d->out_features, f.Dp, f.Wp, d->out_features);
 }
 
 __global__ void mlp_pad_params_kernel(MlpPadMap pm, const float* __restrict__ src, int64_t P, float* __restrict__ dst) {
@@ -573,7 +547,7 @@ static FusedWs fused_ws(const pdeinv_kfp_mlp_desc* d, const FusedShape& f) {
   auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
   w.fl = take(mlpf::workspace_floats(f.Dp, d->n_layers, f.Wp, d->out_features, Bc));
   w.part = take((size_t)PDEINV_GMM_NACC * kLossGrid);
-  w.PP = f.pad ? pad_param_count(width_pad_map(d, f)) : 0;
+  w.PP = f.pad ? width_pad_map(d, f).padded_count() : 0;
   w.pbuf = take((size_t)w.PP);
   w.gbuf = take((size_t)w.PP);
   w.rows = take(f.Dp != d->dim ? (size_t)Bc * 2 * f.Dp : 0);
@@ -852,7 +826,7 @@ extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float
         c.c2 = s.c2; c.c3 = s.c3; c.c0 = s.c0;
         c.ws = wsf; c.Bc = Bc;
         // the initial / terminal sets weight V' (or V) only: no R1 / F2 (kinetic_fokker_planck.py:34-39)
-        c.first_order = s.id != 0 && s.c1 == 0.f && s.c2 == 0.f && first_order_enabled();
+        c.first_order = s.id != 0 && s.c1 == 0.f && s.c2 == 0.f;
         lc.zr = c.z;
         lc.ld = c.ldz;
         const int rc = mlpf::run_chunk(c, mlpf::LossHook{fused_loss_hook, &lc}, st);
@@ -1162,7 +1136,7 @@ KmvFusedPlan kmv_fused_plan(const pdeinv_kmv_mlp_desc* d) {
   k.ni = n <= k.Bc ? (k.Bc / n < n ? k.Bc / n : n) : 1;
   if (k.pad) {
     k.pm = width_pad_map(&m, fs);
-    k.PP = pad_param_count(k.pm);
+    k.PP = k.pm.padded_count();
   }
   size_t o = 0;
   auto take = [&](size_t floats) { const size_t at = o; o += (floats + 63) & ~(size_t)63; return at; };

@@ -17,7 +17,7 @@
 // sum_p A_p^T B_p, rows split into slices (one partial slab each); the 4 pairs of a 16-row block
 // are staged together so every source plane is read once per tile.
 //
-// Per chunk (L = 2; deeper nets add the "middle" steps):
+// Per chunk (run_chunk_full at L = 2; deeper nets add the "middle" steps, one hidden layer runs run_chunk_l1):
 //   FWD   z2 streams = [h1, h1', h1''] K2      A: layer 1 from the rows   E: tanh -> h2, z2', z2''
 //   OUT   y streams  = [h2, h2', h2''] Ko      A: h', h'' from planes   E: +bo, V' and V'' per row
 //   R1    a2 = (2y) Ko^T                                                E: store
@@ -34,8 +34,6 @@
 // First-order chunks (the initial / terminal sets, c1 = c2 = 0; W in {128, 256}) run run_chunk_fo2 instead: the
 // same steps on two streams [h, z'] / [zbar, z'bar], without R1, g, F2 and UB (see there).
 #include <math.h>
-
-#include <stdlib.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -1882,29 +1880,11 @@ static int launch_wgrad_o(WgradArgs a, int64_t part_cap, float* grad_out, float*
   return sum_slabs(a.part, used, (int64_t)a.n_in * a.n_out, grad_out, scratch, st);
 }
 
-// PDEINV_MLP_L1G=0: g = zeta1 K1^T on the VALU kernel (wave reductions) instead of l1_g_mfma_kernel
-static bool use_l1g_mfma() {
-  static const bool on = [] { const char* e = ab_env("PDEINV_MLP_L1G"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// PDEINV_MLP_WGO=0: the output-layer weight gradient on the staged fwgrad kernel (A/B measurements)
-static bool use_wgo() {
-  static const bool on = [] { const char* e = ab_env("PDEINV_MLP_WGO"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-// B-resident row GEMMs / LDS-free weight gradients for W in {128, 256} (PDEINV_MLP_RGEMM=0: the
-// staged fgemm / fwgrad kernels, for A/B measurements)
+// W in {128, 256} runs on the B-resident row GEMMs and the LDS-free weight gradients; the other widths on the
+// staged fgemm / fwgrad kernels.
 // The output layer (K = W, N = out_features <= 64) on the B-resident kernel: one 64-column block, 8 waves
-// of 32 rows x 64 columns (NI = 2), row blocks of 256.
-// PDEINV_MLP_OUT16=0 (A/B): the streamed output-layer products (out_features <= 48) on rgemm's 32-wide tiles instead
-// of rgemm16
-static bool use_out16() {
-  static const bool on = [] { const char* e = ab_env("PDEINV_MLP_OUT16"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
+// of 32 rows x 64 columns (NI = 2), row blocks of 256; its streamed products (S >= 2) with out_features <= 48 on
+// rgemm16's 16-wide tiles.
 template <int S, int AM, int EM>
 static int launch_rgemm16(GemmArgs a, hipStream_t st, int* grid_x_out) {
   constexpr int BNC = 48, BMR = 256;
@@ -1926,7 +1906,7 @@ static int launch_rgemm_out(GemmArgs a, hipStream_t st, int* grid_x_out = nullpt
   // measured no better on them (3.21 -> 3.23-3.45 ms at two workgroups per CU, 3.01 -> 3.04 at one) and stays on rgemm
   // (profiles/r05_c5_out16_nt_ab.txt, r05_c5_nt_hb1_ab.txt)
   if constexpr (S >= 2) {
-    if (a.N <= 48 && use_out16()) return launch_rgemm16<S, AM, EM>(a, st, grid_x_out);
+    if (a.N <= 48) return launch_rgemm16<S, AM, EM>(a, st, grid_x_out);
   }
   constexpr int NI = 2, BNC = 64, BMR = 256;
   if (!(a.K % 64 == 0 && a.K <= 256 && a.N >= 1 && a.N <= BNC))
@@ -1939,20 +1919,6 @@ static int launch_rgemm_out(GemmArgs a, hipStream_t st, int* grid_x_out = nullpt
   if (grid_x_out) *grid_x_out = nrs;
   hipLaunchKernelGGL(kern, dim3(nrs), dim3(kRT), bytes, st, a);
   return check_launch("kfp_mlp fused B-resident output-layer GEMM");
-}
-
-// PDEINV_MLP_RGEMM_OUT=0: the output-layer products on fgemm (A/B)
-static bool use_rgemm_out() {
-  static const bool on = [] { const char* e = ab_env("PDEINV_MLP_RGEMM_OUT"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
-static bool use_rgemm(int W) {
-  static const bool off = [] {
-    const char* e = ab_env("PDEINV_MLP_RGEMM");
-    return e && e[0] == '0';
-  }();
-  return !off && (W == 128 || W == 256);
 }
 
 // any out_features: the output layer's row reductions (E_OUT) take one partial per 64-column block when
@@ -2007,10 +1973,156 @@ static int zero_planes(const std::vector<float*>& planes, size_t n, float* g, si
   return 0;
 }
 
-// PDEINV_MLP_FO2=0 (A/B): first-order chunks run the full three-stream kernels on zeroed g / a / zetabar planes
-static bool use_fo2() {
-  static const bool on = [] { const char* e = ab_env("PDEINV_MLP_FO2"); return !(e && e[0] == '0'); }();
-  return on;
+#define RC(x)          \
+  do {                 \
+    rc = (x);          \
+    if (rc) return rc; \
+  } while (0)
+
+// One chunk's run: what its three chains start from (the workspace planes, the parameter views, the GemmArgs every
+// product copies) and the chains themselves; run_chunk_t picks the chain from the shape and c.first_order.
+namespace {
+template <int D, int WB>
+struct ChunkRun {
+  // hidden-width row-GEMM tiles: 64 x 128 (2 x 2 waves) for W >= 128; narrow nets get tiles no
+  // wider than W (64: 64 x 64, 2 x 2 waves; 32: 128 x 32, 4 x 1 waves) so no MFMA column is padding
+  static constexpr int TN = WB < 128 ? WB : 128;
+  static constexpr int TM = TN == 32 ? 128 : 64;
+  static constexpr int TG = TN == 32 ? 4 : 2;
+  // weight-gradient tiles (>= 64 per side: 2 x 2 waves of 32-multiples)
+  static constexpr int GW = WB < 128 ? 64 : 128;
+  // the B-resident row GEMMs (rgemm) and the LDS-free weight gradients (wgrad2) against the staged fgemm / fwgrad
+  static constexpr bool RG = WB == 128 || WB == 256;
+
+  const Chunk& c;
+  const LossHook& loss;
+  hipStream_t st;
+  int L, W, O;
+  int64_t R;
+  Layout y;
+  float* ws;
+  size_t plane;
+  float *A1, *HB1[3], *Ys[3], *YB[3], *G, *abar0, *part, *part2;
+  float4* terms;
+  const float *prm, *Ko, *bo;
+  GemmArgs base{};
+  int l1_blocks;
+  int64_t l1_rpb;
+
+  ChunkRun(const Chunk& c_, const LossHook& loss_, hipStream_t st_)
+      : c(c_), loss(loss_), st(st_), L(c_.L), W(c_.W), O(c_.O), R(c_.R), y(layout(D, L, W, O, c_.Bc)), ws(c_.ws) {
+    plane = ((size_t)c.Bc * W + 63) & ~(size_t)63;
+    A1 = ws + y.a1;
+    for (int k = 0; k < 3; ++k) {
+      HB1[k] = ws + y.hb1 + k * plane;
+      Ys[k] = ws + y.ys + k * (size_t)c.Bc * O;
+      YB[k] = ws + y.yb + k * (size_t)c.Bc * O;
+    }
+    terms = (float4*)(ws + y.terms);
+    G = ws + y.g;
+    abar0 = ws + y.abar0;
+    part = ws + y.part;
+    part2 = ws + y.part2;
+    prm = c.params;
+    Ko = prm + c.poff[L];
+    bo = prm + c.boff[L];
+    base.R = R;
+    base.c2 = c.c2;
+    base.c3 = c.c3;
+    base.c0 = c.c0;
+    base.part = part;
+    base.xz = c.z;
+    base.ldxz = c.ldz;
+    base.ab0 = abar0;
+    base.k1 = Kw(1);
+    base.b1 = Bw(1);
+    base.wrow = c.wrow;
+    base.ldw = c.ldw;
+    l1_blocks = (int)std::min<int64_t>((R + kL1Rows - 1) / kL1Rows, kRowGridCap);
+    l1_rpb = (R + l1_blocks - 1) / l1_blocks;
+  }
+
+  float* P(int l, int k) const { return ws + y.layer0 + y.layer_stride * (size_t)(l - 2) + plane * k; }
+  const float* Kw(int l) const { return prm + c.poff[l - 1]; }  // hidden layer l (1-based) kernel
+  const float* Bw(int l) const { return prm + c.boff[l - 1]; }
+
+  int sum_terms() const {
+    if (O <= 64) return 0;
+    hipLaunchKernelGGL(terms_sum_kernel, dim3((unsigned)((R + kT - 1) / kT)), dim3(kT), 0, st, terms, (O + 63) / 64, R);
+    return check_launch("kfp_mlp fused terms sum");
+  }
+  int run_g() const {  // g = zeta1 K1^T (grad_x V) from a1
+    if constexpr (WB <= 256) {
+      const int blocks = (int)std::min<int64_t>((R + 63) / 64, 2048);
+      hipLaunchKernelGGL((l1_g_mfma_kernel<D, WB>), dim3(blocks), dim3(kT), 0, st, A1, c.z, c.ldz, Kw(1), Bw(1), R, G);
+      return check_launch("kfp_mlp fused g (MFMA)");
+    } else {
+      const int blocks = (int)std::min<int64_t>((R + 3) / 4, 2048);
+      hipLaunchKernelGGL((l1_g_kernel<D, WB>), dim3(blocks), dim3(kT), 0, st, A1, c.z, c.ldz, Kw(1), Bw(1), R, G);
+      return check_launch("kfp_mlp fused g");
+    }
+  }
+
+  // the three chains (below)
+  int run_chunk_l1() const;
+  int run_chunk_fo2() const;
+  int run_chunk_full() const;
+};
+
+// One hidden layer: the output layer reads the layer-1 streams straight from the prologue modes (h1,
+// s1 z1', s2 z1'^2 | s1 (abar0 K1)), the reverse product stops at hbar1 (l1_grad_kernel), and the
+// output-layer weight gradient rebuilds the layer-1 streams from the rows (GA_L1) — no plane of
+// layer 1 is stored
+template <int D, int WB>
+int ChunkRun<D, WB>::run_chunk_l1() const {
+  int rc = 0;
+  {
+    GemmArgs a = base;
+    a.K = W; a.N = O; a.Bw = Ko; a.bias = bo;
+    a.po0 = Ys[0]; a.po1 = Ys[1]; a.po2 = Ys[2]; a.terms = terms;
+    RC((launch_gemm<3, 128, 64, 4, A_L1F, B_NN, E_OUT, D>(a, st)));
+    RC(sum_terms());
+  }
+  if (c.first_order) {
+    RC(zero_planes({A1}, (size_t)R * W, G, (size_t)R * D, st));
+  } else {
+    {
+      GemmArgs a = base;
+      a.K = O; a.N = W; a.Bw = Ko; a.pa0 = Ys[0]; a.po0 = A1;
+      RC((launch_gemm1<A_U, B_NT>(a, st)));
+    }
+    RC(run_g());
+  }
+  if (c.grad_only) return 0;
+  RC(loss.fn(loss.ctx, G, terms, abar0, R, st));
+  {
+    GemmArgs a = base;
+    a.K = W; a.N = O; a.Bw = Ko;
+    a.pe0 = Ys[0]; a.pe1 = Ys[1]; a.pe2 = Ys[2];
+    a.po0 = YB[0]; a.po1 = YB[1]; a.po2 = YB[2];
+    int gx = 0;
+    RC((launch_gemm<1, 128, 64, 4, A_L1A, B_NN, E_SEEDS, D>(a, st, &gx)));
+    RC(sum_slabs(part, gx, O, c.grad + c.boff[L], part2, st));
+  }
+  {
+    GemmArgs a = base;
+    a.K = O; a.N = W; a.Bw = Ko;
+    a.pa0 = YB[0]; a.pa1 = YB[1]; a.pa2 = YB[2];
+    a.po0 = HB1[0]; a.po1 = HB1[1]; a.po2 = HB1[2];
+    RC((launch_gemm<3, TM, TN, TG, A_S3, B_NT, E_STORE3>(a, st)));
+    hipLaunchKernelGGL((l1_grad_kernel<D, WB>), dim3(l1_blocks), dim3(kT), 0, st, HB1[0], HB1[1], HB1[2], A1, c.z,
+                       c.ldz, abar0, Kw(1), Bw(1), R, l1_rpb, part);
+    RC(check_launch("kfp_mlp fused layer-1 gradient"));
+    RC(sum_slabs(part, l1_blocks, (int64_t)(D + 1) * W, c.grad + c.poff[0], part2, st));  // K1 then b1
+  }
+  {
+    WgradArgs g{};
+    g.R = R; g.n_in = W; g.n_out = O; g.part = part;
+    g.xz = c.z; g.ldxz = c.ldz; g.ab0 = abar0; g.k1 = Kw(1); g.b1 = Bw(1);
+    g.pb0 = YB[0]; g.pb1 = YB[1]; g.pb2 = YB[2]; g.pb3 = Ys[0];
+    RC((launch_wgrad<GW, 64, GA_L1, GB_SM, D>(g, c.grad + c.poff[L], part2, st)));
+  }
+  return 0;
 }
 
 // The first-order chain (initial / terminal sets: c1 = c2 = 0, kinetic_fokker_planck.py:34-39) on two streams, L >= 2,
@@ -2022,47 +2134,9 @@ static bool use_fo2() {
 //   R2    [hbar_L, h'bar_L] = [ybar, y'bar] Ko^T, act_bwd (S = 2) ... [hbar1, h'bar1] = [zbar2, z'bar2] K2^T
 //   L1    l1_grad_kernel<FO>;  G: wgrad_o / wgrad2 with 2 pairs
 template <int D, int WB>
-static int run_chunk_fo2(const Chunk& c, const LossHook& loss, hipStream_t st) {
-  constexpr int TN = WB < 128 ? WB : 128;
-  constexpr int TM = TN == 32 ? 128 : 64;
-  constexpr int TG = TN == 32 ? 4 : 2;
-  static_assert(WB == 128 || WB == 256, "first-order chain: the B-resident kernels");
-  const int L = c.L, W = c.W, O = c.O;
-  const int64_t R = c.R;
-  const Layout y = layout(D, L, W, O, c.Bc);
-  float* ws = c.ws;
-  const size_t plane = ((size_t)c.Bc * W + 63) & ~(size_t)63;
-  auto P = [&](int l, int k) { return ws + y.layer0 + y.layer_stride * (size_t)(l - 2) + plane * k; };
-  float* HB1[2] = {ws + y.hb1, ws + y.hb1 + plane};
-  float* YB[2] = {ws + y.yb, ws + y.yb + (size_t)c.Bc * O};
-  float4* terms = (float4*)(ws + y.terms);
-  float* G = ws + y.g;
-  float* abar0 = ws + y.abar0;
-  float* part = ws + y.part;
-  float* part2 = ws + y.part2;
-  const float* prm = c.params;
-  auto Kw = [&](int l) { return prm + c.poff[l - 1]; };
-  auto Bw = [&](int l) { return prm + c.boff[l - 1]; };
-  const float* Ko = prm + c.poff[L];
-  GemmArgs base{};
-  base.R = R;
-  base.c2 = 0.f;
-  base.c3 = c.c3;
-  base.c0 = c.c0;
-  base.part = part;
-  base.xz = c.z;
-  base.ldxz = c.ldz;
-  base.ab0 = abar0;
-  base.k1 = Kw(1);
-  base.b1 = Bw(1);
-  base.wrow = c.wrow;
-  base.ldw = c.ldw;
+int ChunkRun<D, WB>::run_chunk_fo2() const {
+  static_assert(RG, "first-order chain: the B-resident kernels");
   int rc = 0;
-#define RC(x)          \
-  do {                 \
-    rc = (x);          \
-    if (rc) return rc; \
-  } while (0)
   {
     GemmArgs a = base;
     a.K = W; a.N = W; a.Bw = Kw(2); a.bias = Bw(2);
@@ -2114,8 +2188,6 @@ static int run_chunk_fo2(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.pa0 = P(2, P_ZB0); a.pa1 = P(2, P_ZB1);
     a.po0 = HB1[0]; a.po1 = HB1[1];
     RC((launch_rgemm<2, A_S2, B_NT, E_STORE3>(a, st)));
-    const int l1_blocks = (int)std::min<int64_t>((R + kL1Rows - 1) / kL1Rows, kRowGridCap);
-    const int64_t l1_rpb = (R + l1_blocks - 1) / l1_blocks;
     hipLaunchKernelGGL((l1_grad_kernel<D, WB, true>), dim3(l1_blocks), dim3(kT), 0, st, HB1[0], HB1[1], nullptr,
                        nullptr, c.z, c.ldz, nullptr, Kw(1), Bw(1), R, l1_rpb, part);
     RC(check_launch("kfp_mlp fused layer-1 gradient (first order)"));
@@ -2148,143 +2220,20 @@ static int run_chunk_fo2(const Chunk& c, const LossHook& loss, hipStream_t st) {
     g.pb0 = P(2, P_ZB0); g.pb1 = P(2, P_ZB1);
     RC((launch_wgrad2<WB / 128, WB / 64, GA_L1, GB_PL, D, 2>(g, c.grad + c.poff[1], part2, st)));
   }
-#undef RC
   return 0;
 }
 
+// The full second-order chain, L >= 2. A first-order chunk outside run_chunk_fo2's shapes runs it on zeroed
+// g / a / zetabar planes.
 template <int D, int WB>
-static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
-  // hidden-width row-GEMM tiles: 64 x 128 (2 x 2 waves) for W >= 128; narrow nets get tiles no
-  // wider than W (64: 64 x 64, 2 x 2 waves; 32: 128 x 32, 4 x 1 waves) so no MFMA column is padding
-  constexpr int TN = WB < 128 ? WB : 128;
-  constexpr int TM = TN == 32 ? 128 : 64;
-  constexpr int TG = TN == 32 ? 4 : 2;
-  // weight-gradient tiles (>= 64 per side: 2 x 2 waves of 32-multiples)
-  constexpr int GW = WB < 128 ? 64 : 128;
-  const int L = c.L, W = c.W, O = c.O;
-  const int64_t R = c.R;
-  const Layout y = layout(D, L, W, O, c.Bc);
-  const bool RG = use_rgemm(WB);
-  float* ws = c.ws;
-  const size_t plane = ((size_t)c.Bc * W + 63) & ~(size_t)63;
-  auto P = [&](int l, int k) { return ws + y.layer0 + y.layer_stride * (size_t)(l - 2) + plane * k; };
-  float* A1 = ws + y.a1;
-  float* HB1[3] = {ws + y.hb1, ws + y.hb1 + plane, ws + y.hb1 + 2 * plane};
-  float* Ys[3] = {ws + y.ys, ws + y.ys + (size_t)c.Bc * O, ws + y.ys + 2 * (size_t)c.Bc * O};
-  float* YB[3] = {ws + y.yb, ws + y.yb + (size_t)c.Bc * O, ws + y.yb + 2 * (size_t)c.Bc * O};
-  float4* terms = (float4*)(ws + y.terms);
-  float* G = ws + y.g;
-  float* abar0 = ws + y.abar0;
-  float* part = ws + y.part;
-  float* part2 = ws + y.part2;
-  const float* prm = c.params;
-  auto Kw = [&](int l) { return prm + c.poff[l - 1]; };  // hidden layer l (1-based) kernel
-  auto Bw = [&](int l) { return prm + c.boff[l - 1]; };
-  const float* Ko = prm + c.poff[L];
-  const float* bo = prm + c.boff[L];
-
-  GemmArgs base{};
-  base.R = R;
-  base.c2 = c.c2;
-  base.c3 = c.c3;
-  base.c0 = c.c0;
-  base.part = part;
-  base.xz = c.z;
-  base.ldxz = c.ldz;
-  base.ab0 = abar0;
-  base.k1 = Kw(1);
-  base.b1 = Bw(1);
-  base.wrow = c.wrow;
-  base.ldw = c.ldw;
+int ChunkRun<D, WB>::run_chunk_full() const {
   int rc = 0;
-#define RC(x)          \
-  do {                 \
-    rc = (x);          \
-    if (rc) return rc; \
-  } while (0)
-
-  const int l1_blocks = (int)std::min<int64_t>((R + kL1Rows - 1) / kL1Rows, kRowGridCap);
-  const int64_t l1_rpb = (R + l1_blocks - 1) / l1_blocks;
-  auto sum_terms = [&]() {
-    if (O <= 64) return 0;
-    hipLaunchKernelGGL(terms_sum_kernel, dim3((unsigned)((R + kT - 1) / kT)), dim3(kT), 0, st, terms, (O + 63) / 64, R);
-    return check_launch("kfp_mlp fused terms sum");
-  };
-  auto run_g = [&]() {  // g = zeta1 K1^T (grad_x V) from a1
-    if constexpr (WB <= 256) {
-      if (use_l1g_mfma()) {
-        const int blocks = (int)std::min<int64_t>((R + 63) / 64, 2048);
-        hipLaunchKernelGGL((l1_g_mfma_kernel<D, WB>), dim3(blocks), dim3(kT), 0, st, A1, c.z, c.ldz, Kw(1), Bw(1), R, G);
-        return check_launch("kfp_mlp fused g (MFMA)");
-      }
-    }
-    const int blocks = (int)std::min<int64_t>((R + 3) / 4, 2048);
-    hipLaunchKernelGGL((l1_g_kernel<D, WB>), dim3(blocks), dim3(kT), 0, st, A1, c.z, c.ldz, Kw(1), Bw(1), R, G);
-    return check_launch("kfp_mlp fused g");
-  };
-  if (L == 1) {
-    // one hidden layer: the output layer reads the layer-1 streams straight from the prologue modes (h1,
-    // s1 z1', s2 z1'^2 | s1 (abar0 K1)), the reverse product stops at hbar1 (l1_grad_kernel), and the
-    // output-layer weight gradient rebuilds the layer-1 streams from the rows (GA_L1) — no plane of
-    // layer 1 is stored
-    {
-      GemmArgs a = base;
-      a.K = W; a.N = O; a.Bw = Ko; a.bias = bo;
-      a.po0 = Ys[0]; a.po1 = Ys[1]; a.po2 = Ys[2]; a.terms = terms;
-      RC((launch_gemm<3, 128, 64, 4, A_L1F, B_NN, E_OUT, D>(a, st)));
-      RC(sum_terms());
-    }
-    if (c.first_order) {
-      RC(zero_planes({A1}, (size_t)R * W, G, (size_t)R * D, st));
-    } else {
-      {
-        GemmArgs a = base;
-        a.K = O; a.N = W; a.Bw = Ko; a.pa0 = Ys[0]; a.po0 = A1;
-        RC((launch_gemm1<A_U, B_NT>(a, st)));
-      }
-      RC(run_g());
-    }
-    if (c.grad_only) return 0;
-    RC(loss.fn(loss.ctx, G, terms, abar0, R, st));
-    {
-      GemmArgs a = base;
-      a.K = W; a.N = O; a.Bw = Ko;
-      a.pe0 = Ys[0]; a.pe1 = Ys[1]; a.pe2 = Ys[2];
-      a.po0 = YB[0]; a.po1 = YB[1]; a.po2 = YB[2];
-      int gx = 0;
-      RC((launch_gemm<1, 128, 64, 4, A_L1A, B_NN, E_SEEDS, D>(a, st, &gx)));
-      RC(sum_slabs(part, gx, O, c.grad + c.boff[L], part2, st));
-    }
-    {
-      GemmArgs a = base;
-      a.K = O; a.N = W; a.Bw = Ko;
-      a.pa0 = YB[0]; a.pa1 = YB[1]; a.pa2 = YB[2];
-      a.po0 = HB1[0]; a.po1 = HB1[1]; a.po2 = HB1[2];
-      RC((launch_gemm<3, TM, TN, TG, A_S3, B_NT, E_STORE3>(a, st)));
-      hipLaunchKernelGGL((l1_grad_kernel<D, WB>), dim3(l1_blocks), dim3(kT), 0, st, HB1[0], HB1[1], HB1[2], A1, c.z,
-                         c.ldz, abar0, Kw(1), Bw(1), R, l1_rpb, part);
-      RC(check_launch("kfp_mlp fused layer-1 gradient"));
-      RC(sum_slabs(part, l1_blocks, (int64_t)(D + 1) * W, c.grad + c.poff[0], part2, st));  // K1 then b1
-    }
-    {
-      WgradArgs g{};
-      g.R = R; g.n_in = W; g.n_out = O; g.part = part;
-      g.xz = c.z; g.ldxz = c.ldz; g.ab0 = abar0; g.k1 = Kw(1); g.b1 = Bw(1);
-      g.pb0 = YB[0]; g.pb1 = YB[1]; g.pb2 = YB[2]; g.pb3 = Ys[0];
-      RC((launch_wgrad<GW, 64, GA_L1, GB_SM, D>(g, c.grad + c.poff[L], part2, st)));
-    }
-    return 0;
-  }
-  if constexpr (WB == 128 || WB == 256) {
-    if (c.first_order && !c.grad_only && c.c2 == 0.f && RG && O <= 64 && use_rgemm_out() && use_wgo() && use_fo2())
-      return run_chunk_fo2<D, WB>(c, loss, st);
-  }
   // ---- F1 -------------------------------------------------------------------------------
   {  // layer 1 in the prologue (h1 streams never stored), layer 2 on MFMA
     GemmArgs a = base;
     a.K = W; a.N = W; a.Bw = Kw(2); a.bias = Bw(2);
     a.po0 = P(2, P_H); a.po1 = P(2, P_ZD); a.po2 = P(2, P_ZDD);
-    if (RG) RC((launch_rgemm<3, A_L1F, B_NN, E_ACT_FWD, D>(a, st)));
+    if constexpr (RG) RC((launch_rgemm<3, A_L1F, B_NN, E_ACT_FWD, D>(a, st)));
     else RC((launch_gemm<3, TM, TN, TG, A_L1F, B_NN, E_ACT_FWD, D>(a, st)));
   }
   for (int l = 3; l <= L; ++l) {
@@ -2292,7 +2241,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.K = W; a.N = W; a.Bw = Kw(l); a.bias = Bw(l);
     a.pa0 = P(l - 1, P_H); a.pa1 = P(l - 1, P_ZD); a.pa2 = P(l - 1, P_ZDD);
     a.po0 = P(l, P_H); a.po1 = P(l, P_ZD); a.po2 = P(l, P_ZDD);
-    if (RG) RC((launch_rgemm<3, A_FWD, B_NN, E_ACT_FWD>(a, st)));
+    if constexpr (RG) RC((launch_rgemm<3, A_FWD, B_NN, E_ACT_FWD>(a, st)));
     else RC((launch_gemm<3, TM, TN, TG, A_FWD, B_NN, E_ACT_FWD>(a, st)));
   }
   {
@@ -2300,7 +2249,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.K = W; a.N = O; a.Bw = Ko; a.bias = bo;
     a.pa0 = P(L, P_H); a.pa1 = P(L, P_ZD); a.pa2 = P(L, P_ZDD);
     a.po0 = Ys[0]; a.po1 = Ys[1]; a.po2 = Ys[2]; a.terms = terms;
-    if (RG && use_rgemm_out() && O <= 64) RC((launch_rgemm_out<3, A_FWD, E_OUT>(a, st)));
+    if (RG && O <= 64) RC((launch_rgemm_out<3, A_FWD, E_OUT>(a, st)));
     else RC((launch_gemm<3, 128, 64, 4, A_FWD, B_NN, E_OUT>(a, st)));
     RC(sum_terms());
   }
@@ -2322,7 +2271,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
       GemmArgs a = base;
       a.K = W; a.N = W; a.Bw = Kw(l); a.pa0 = P(l, P_H); a.pa1 = P(l, P_A);
       a.po0 = l > 2 ? P(l - 1, P_A) : A1;
-      if (RG) RC((launch_rgemm<1, A_S1MUL, B_NT, E_STORE>(a, st)));
+      if constexpr (RG) RC((launch_rgemm<1, A_S1MUL, B_NT, E_STORE>(a, st)));
       else RC((launch_gemm1<A_S1MUL, B_NT>(a, st)));
     }
     RC(run_g());
@@ -2334,14 +2283,14 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     {  // abar1 = s1(z1) (abar0 K1) in the prologue
       GemmArgs a = base;
       a.K = W; a.N = W; a.Bw = Kw(2); a.po0 = P(2, P_ZETABAR);
-      if (RG) RC((launch_rgemm<1, A_L1A, B_NN, E_STORE, D>(a, st)));
+      if constexpr (RG) RC((launch_rgemm<1, A_L1A, B_NN, E_STORE, D>(a, st)));
       else RC((launch_gemm1<A_L1A, B_NN, D>(a, st)));
     }
     for (int l = 3; l <= L; ++l) {
       GemmArgs a = base;
       a.K = W; a.N = W; a.Bw = Kw(l); a.pa0 = P(l - 1, P_H); a.pa1 = P(l - 1, P_ZETABAR);
       a.po0 = P(l, P_ZETABAR);
-      if (RG) RC((launch_rgemm<1, A_S1MUL, B_NN, E_STORE>(a, st)));
+      if constexpr (RG) RC((launch_rgemm<1, A_S1MUL, B_NN, E_STORE>(a, st)));
       else RC((launch_gemm1<A_S1MUL, B_NN>(a, st)));
     }
   }
@@ -2351,7 +2300,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.pe0 = Ys[0]; a.pe1 = Ys[1]; a.pe2 = Ys[2];
     a.po0 = YB[0]; a.po1 = YB[1]; a.po2 = YB[2];
     int gx = 0;
-    if (RG && use_rgemm_out() && O <= 64) RC((launch_rgemm_out<1, A_S1MUL, E_SEEDS>(a, st, &gx)));
+    if (RG && O <= 64) RC((launch_rgemm_out<1, A_S1MUL, E_SEEDS>(a, st, &gx)));
     else RC((launch_gemm<1, 128, 64, 4, A_S1MUL, B_NN, E_SEEDS>(a, st, &gx)));
     RC(sum_slabs(part, gx, O, c.grad + c.boff[L], part2, st));
   }
@@ -2374,7 +2323,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.pe4 = P(l - 1, P_ZETABAR);
     a.po0 = P(l - 1, P_ZB0); a.po1 = P(l - 1, P_ZB1); a.po2 = P(l - 1, P_ZB2);
     int gx = 0;
-    if (RG) RC((launch_rgemm<3, A_S3, B_NT, E_ACT_BWD>(a, st, &gx)));
+    if constexpr (RG) RC((launch_rgemm<3, A_S3, B_NT, E_ACT_BWD>(a, st, &gx)));
     else RC((launch_gemm<3, TM, TN, TG, A_S3, B_NT, E_ACT_BWD>(a, st, &gx)));
     RC(sum_slabs(part, gx, W, c.grad + c.boff[l - 2], part2, st));
   }
@@ -2383,7 +2332,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     a.K = W; a.N = W; a.Bw = Kw(2);
     a.pa0 = P(2, P_ZB0); a.pa1 = P(2, P_ZB1); a.pa2 = P(2, P_ZB2);
     a.po0 = HB1[0]; a.po1 = HB1[1]; a.po2 = HB1[2];
-    if (RG) RC((launch_rgemm<3, A_S3, B_NT, E_STORE3>(a, st)));
+    if constexpr (RG) RC((launch_rgemm<3, A_S3, B_NT, E_STORE3>(a, st)));
     else RC((launch_gemm<3, TM, TN, TG, A_S3, B_NT, E_STORE3>(a, st)));
     hipLaunchKernelGGL((l1_grad_kernel<D, WB>), dim3(l1_blocks), dim3(kT), 0, st, HB1[0], HB1[1], HB1[2], A1, c.z,
                        c.ldz, abar0, Kw(1), Bw(1), R, l1_rpb, part);
@@ -2397,7 +2346,7 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     g.pa0 = P(L, P_H); g.pa1 = P(L, P_ZD); g.pa2 = P(L, P_ZDD); g.pa3 = P(L, P_ZETABAR);
     g.pb0 = YB[0]; g.pb1 = YB[1]; g.pb2 = YB[2]; g.pb3 = Ys[0];
     const int64_t cap = (int64_t)part_floats(D, W, O);
-    if (WB >= 64 && WB <= 256 && O <= 64 && use_wgo()) {
+    if (WB >= 64 && WB <= 256 && O <= 64) {
       switch ((O + 15) / 16) {
         case 1: RC((launch_wgrad_o<1>(g, cap, c.grad + c.poff[L], part2, st))); break;
         case 2: RC((launch_wgrad_o<2>(g, cap, c.grad + c.poff[L], part2, st))); break;
@@ -2413,27 +2362,31 @@ static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
     g.R = R; g.n_in = W; g.n_out = W; g.part = part;
     g.pa0 = P(l - 1, P_H); g.pa1 = P(l - 1, P_ZD); g.pa2 = P(l - 1, P_ZDD); g.pa3 = P(l - 1, P_ZETABAR);
     g.pb0 = P(l, P_ZB0); g.pb1 = P(l, P_ZB1); g.pb2 = P(l, P_ZB2); g.pb3 = P(l, P_H); g.pb4 = P(l, P_A);
-    if constexpr (WB == 128 || WB == 256) {
-      if (RG) RC((launch_wgrad2<WB / 128, WB / 64, GA_PL, GB_PL>(g, c.grad + c.poff[l - 1], part2, st)));
-      else RC((launch_wgrad<GW, GW, GA_PL, GB_PL>(g, c.grad + c.poff[l - 1], part2, st)));
-    } else {
-      RC((launch_wgrad<GW, GW, GA_PL, GB_PL>(g, c.grad + c.poff[l - 1], part2, st)));
-    }
+    if constexpr (RG) RC((launch_wgrad2<WB / 128, WB / 64, GA_PL, GB_PL>(g, c.grad + c.poff[l - 1], part2, st)));
+    else RC((launch_wgrad<GW, GW, GA_PL, GB_PL>(g, c.grad + c.poff[l - 1], part2, st)));
   }
   {
     WgradArgs g{};
     g.R = R; g.n_in = W; g.n_out = W; g.part = part;
     g.xz = c.z; g.ldxz = c.ldz; g.ab0 = abar0; g.k1 = Kw(1); g.b1 = Bw(1);
     g.pb0 = P(2, P_ZB0); g.pb1 = P(2, P_ZB1); g.pb2 = P(2, P_ZB2); g.pb3 = P(2, P_H); g.pb4 = P(2, P_A);
-    if constexpr (WB == 128 || WB == 256) {
-      if (RG) RC((launch_wgrad2<WB / 128, WB / 64, GA_L1, GB_PL, D>(g, c.grad + c.poff[1], part2, st)));
-      else RC((launch_wgrad<GW, GW, GA_L1, GB_PL, D>(g, c.grad + c.poff[1], part2, st)));
-    } else {
-      RC((launch_wgrad<GW, GW, GA_L1, GB_PL, D>(g, c.grad + c.poff[1], part2, st)));
-    }
+    if constexpr (RG) RC((launch_wgrad2<WB / 128, WB / 64, GA_L1, GB_PL, D>(g, c.grad + c.poff[1], part2, st)));
+    else RC((launch_wgrad<GW, GW, GA_L1, GB_PL, D>(g, c.grad + c.poff[1], part2, st)));
   }
-#undef RC
   return 0;
+}
+
+#undef RC
+}  // namespace
+
+template <int D, int WB>
+static int run_chunk_t(const Chunk& c, const LossHook& loss, hipStream_t st) {
+  const ChunkRun<D, WB> run(c, loss, st);
+  if (c.L == 1) return run.run_chunk_l1();
+  if constexpr (ChunkRun<D, WB>::RG) {
+    if (c.first_order && !c.grad_only && c.c2 == 0.f && c.O <= 64) return run.run_chunk_fo2();
+  }
+  return run.run_chunk_full();
 }
 
 template <int D>

@@ -24,7 +24,6 @@
 // Widths / dims between the compiled ones are zero-padded on the device (exact: padded units carry
 // z = 0, h = tanh 0 = 0 and zero outgoing weights).
 #include <math.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -670,15 +669,6 @@ __global__ void kmvp_reduce_kernel(MlpPadMap pm, const float* __restrict__ gslab
 namespace {
 constexpr int kPairWaves = 2048;  // persistent grid: 2 waves per SIMD of 256 CUs
 
-int pair_waves() {
-  static const int w = [] {
-    const char* e = ab_env("PDEINV_PAIR_WAVES");  // A/B experiments (tools)
-    const int v = e ? atoi(e) : kPairWaves;
-    return v >= 2 ? v & ~1 : kPairWaves;
-  }();
-  return w;
-}
-
 int pad_dim(int d) { return d <= 2 ? 2 : (d <= 4 ? 4 : 8); }
 int pad_width(int w) { return w <= 8 ? 8 : (w <= 16 ? 16 : (w <= 20 ? 20 : (w <= 24 ? 24 : 28))); }
 
@@ -694,21 +684,11 @@ PairPlan pair_plan(const pdeinv_kmv_mlp_desc* d) {
   p.DP = pad_dim(d->dim);
   p.WP = pad_width(d->width);
   const int L = d->n_layers;
-  p.pm.L = L;
-  int64_t ro = 0, po = 0;
-  for (int l = 0; l <= L; ++l) {
-    p.pm.din[l] = l == 0 ? d->dim : d->width;
-    p.pm.dout[l] = l == L ? d->out_features : d->width;
-    p.pm.pin[l] = l == 0 ? p.DP : p.WP;
-    p.pm.pout[l] = l == L ? (d->out_features + mlpp::kOC - 1) / mlpp::kOC * mlpp::kOC : p.WP;
-    p.pm.roff[l] = ro;
-    p.pm.poff[l] = po;
-    ro += (int64_t)p.pm.din[l] * p.pm.dout[l] + p.pm.dout[l];
-    po += (int64_t)p.pm.pin[l] * p.pm.pout[l] + p.pm.pout[l];
-  }
-  p.P = po;
+  p.pm = mlp_pad_map(d->dim, d->width, L, d->out_features, p.DP, p.WP,
+                     (d->out_features + mlpp::kOC - 1) / mlpp::kOC * mlpp::kOC);
+  p.P = p.pm.padded_count();
   p.items = (int64_t)d->n_sets * d->n_rows;
-  p.n_waves = p.items < pair_waves() ? ((p.items + 1) / 2) * 2 : pair_waves();
+  p.n_waves = p.items < kPairWaves ? ((p.items + 1) / 2) * 2 : kPairWaves;
   size_t o = 0;
   auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
   p.off_prm = take(sizeof(float) * p.P);
@@ -739,10 +719,6 @@ void launch_pairs(const mlpp::Args& a, int64_t n_waves, hipStream_t st, bool pas
 
 template <int D>
 int dispatch_w(int WP, const mlpp::Args& a, int64_t nw, hipStream_t st, bool pass2) {
-#ifdef PDEINV_PAIRS_QUICK  // development builds: one instantiation
-  if (D == 2 && WP == 20) { launch_pairs<2, 20>(a, nw, st, pass2); return PDEINV_OK; }
-  return fail(PDEINV_ERR_UNSUPPORTED, "quick build");
-#else
   switch (WP) {
     case 8: launch_pairs<D, 8>(a, nw, st, pass2); break;
     case 16: launch_pairs<D, 16>(a, nw, st, pass2); break;
@@ -752,7 +728,6 @@ int dispatch_w(int WP, const mlpp::Args& a, int64_t nw, hipStream_t st, bool pas
     default: return fail(PDEINV_ERR_UNSUPPORTED, "kmv_mlp pairs: width");
   }
   return PDEINV_OK;
-#endif
 }
 }  // namespace
 

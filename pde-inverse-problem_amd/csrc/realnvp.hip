@@ -169,16 +169,9 @@ __global__ __launch_bounds__(kBlock) void realnvp_logdensity_kernel(NvpArgs a, c
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kNvpMaxRows = 8192;  // slab rows (128-sample blocks) per launch + reduce chunk
-#ifndef PDEINV_NVT
-#define PDEINV_NVT 2
-#endif
-#ifndef PDEINV_NVW_PK
-#define PDEINV_NVW_PK 3  // waves per SIMD of the packed-layout gradient kernel (49 KB LDS per block)
-#endif
-#ifndef PDEINV_NVW
-#define PDEINV_NVW 2
-#endif
-constexpr int kNvT = PDEINV_NVT;   // 16-sample tiles per wave (32 samples; 128 per block)
+constexpr int kNvT = 2;            // 16-sample tiles per wave (32 samples; 128 per block)
+constexpr int kNvWavesPk = 3;      // waves per SIMD of the packed-layout gradient kernel (49 KB LDS per block)
+constexpr int kNvWaves = 2;        // waves per SIMD of the identity-layout gradient kernel
 constexpr int kNvSPB = kWavesPerBlock * 16 * kNvT;  // samples per block = per slab row
 constexpr int kNvWS = 20;          // LDS row stride of a padded 16 x 16 weight matrix
 // Per-wave sample stage: [16 samples][16 components] dense, the 4-float chunk c of sample row r stored at chunk
@@ -611,7 +604,7 @@ __device__ __forceinline__ uint32_t nv_layer_dst(int k, int d, int n_t) {
 }
 
 template <int ACT, bool PK>
-__global__ __launch_bounds__(kBlock, PK ? PDEINV_NVW_PK : PDEINV_NVW) void realnvp_grad_kernel(NvpArgs a, int d, const float* __restrict__ params,
+__global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_grad_kernel(NvpArgs a, int d, const float* __restrict__ params,
                                                                  const float* __restrict__ tv, int64_t t_stride,
                                                                  const float* __restrict__ xv, int64_t n, int64_t ld,
                                                                  int64_t layer_stride, int64_t n_params,
@@ -957,9 +950,6 @@ __global__ __launch_bounds__(kBlock, PK ? PDEINV_NVW_PK : PDEINV_NVW) void realn
 // lane), then the splits in order. Column c of parts is reference parameter c (n_params: the loss),
 // read from slab column nv_slab_col(c). On the last chunk grad[c] = scale * acc[c] (c < n_params) and
 // loss = scale * acc[n_params].
-#ifndef PDEINV_NVP_TIME_AUTO_MFMA
-#define PDEINV_NVP_TIME_AUTO_MFMA 1  // by measurement: faster than the general path on both batches
-#endif
 constexpr int kNvSplits = 16;
 __global__ __launch_bounds__(kBlock) void nvp_slab_split_kernel(const float* __restrict__ slab_base, int rows,
                                                                  int64_t ld, NvSlabMap map, int64_t n_cols,
@@ -1365,10 +1355,8 @@ __device__ __forceinline__ void nv_mlp_fwd3(const float* p, const NvLane& ln, co
   nv_fwdT3(p + M::W3, ln, z, out);
 }
 
-#ifndef PDEINV_NVW_TIME
-#define PDEINV_NVW_TIME 2
-#endif
-__global__ __launch_bounds__(kBlock, PDEINV_NVW_TIME) void realnvp_time_mfma_kernel(
+constexpr int kNvWavesTime = 2;  // waves per SIMD of the matrix-core time-derivative kernel
+__global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel(
     NvpArgs a, NvFreq fr, int d, const float* __restrict__ params, const float* __restrict__ tv, int64_t t_stride,
     const float* __restrict__ xv, int64_t n, int64_t ld, int64_t n_rows, int64_t set_stride, int64_t layer_stride,
     float* __restrict__ logp, float* __restrict__ ds) {
@@ -1606,12 +1594,8 @@ extern "C" int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* d, const flo
   return check_launch("realnvp_logdensity_kernel");
 }
 
-// Packed layout where [x | temb] fits one 16-vector with x in register 0 (PDEINV_NVP_PACK=0 forces the
-// identity layout, A/B).
-static bool nvp_packed(const pdeinv_realnvp_desc* d) {
-  static const bool pack_env = [] { const char* e = ab_env("PDEINV_NVP_PACK"); return !(e && e[0] == '0'); }();
-  return pack_env && d->dim <= 4 && in_dim_of(d) - d->dim <= 12;
-}
+// Packed layout where [x | temb] fits one 16-vector with x in register 0; the identity layout otherwise (d > 4)
+static bool nvp_packed(const pdeinv_realnvp_desc* d) { return d->dim <= 4 && in_dim_of(d) - d->dim <= 12; }
 static NvSlabMap nvp_slab_map(const pdeinv_realnvp_desc* d) {
   NvSlabMap m{};
   const int E = d->ignore_time ? 0 : d->embed_time_dim;
@@ -1712,8 +1696,9 @@ static bool nvp_time_mfma_ok(const pdeinv_realnvp_desc* d) {
   return (d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU) && d->dim <= 4 && !d->ignore_time &&
          d->embed_time_dim >= 4 && d->embed_time_dim <= 12;
 }
-// AUTO takes the matrix-core path only where it measured faster than the general path (DESIGN.md §4.2.1).
-static bool nvp_time_auto_mfma(const pdeinv_realnvp_desc* d) { return PDEINV_NVP_TIME_AUTO_MFMA && nvp_time_mfma_ok(d); }
+// AUTO takes the matrix-core path only where it measured faster than the general path.
+constexpr bool kNvTimeAutoMfma = true;  // by measurement: faster than the general path on both batches
+static bool nvp_time_auto_mfma(const pdeinv_realnvp_desc* d) { return kNvTimeAutoMfma && nvp_time_mfma_ok(d); }
 
 // Shared by the two time-derivative entry points: n_rows == 0 is the per-sample view (t_stride), n_rows > 0 the
 // sets view (realnvp_time_kernel).

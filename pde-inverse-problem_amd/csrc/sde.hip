@@ -159,7 +159,7 @@ __global__ __launch_bounds__(kBlock, MINW) void sde_simulate_kernel(SdeArgs a, c
   static_assert(!RES || (POT == PDEINV_POT_GMM && !MOM), "the fused residual is the GMM simulator's");
   static_assert(!NXT || (POT == PDEINV_POT_MEANFIELD_QUADRATIC && !NOISE && M % 4 == 0 && D <= 8),
                 "next-simulate sums: McKean–Vlasov, Philox noise, even dim <= 8 (staged stores)");
-  const int bid = a.remap ? xcd_block(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int bid = xcd_block(blockIdx.x, gridDim.x);
   const int64_t i_raw = (int64_t)bid * kBlock + threadIdx.x;
   const bool active = i_raw < a.N;
   const int64_t i = active ? i_raw : a.N - 1;  // inactive lanes compute on a valid row, store nothing

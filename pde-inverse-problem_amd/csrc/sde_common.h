@@ -4,7 +4,6 @@
 #pragma once
 #include <math.h>
 #include <stddef.h>
-#include <stdlib.h>
 
 #include <cmath>
 
@@ -15,7 +14,6 @@ namespace pdeinv {
 struct SdeArgs {
   int64_t N, poff, ld_z0;
   int32_t n_steps, random_shift, K, has_center;
-  int32_t remap;  // 1 (default): XCD-contiguous block order (xcd_block); PDEINV_SIM_REMAP=0 disables
   float dt, gamma, ns, neg_half_inv_s2_log2e, inv_s2, l2s;
   uint32_t k0, k1, ctr_off;
   const float* noise;
@@ -173,10 +171,6 @@ static inline int build_args(const pdeinv_sde_desc* d, SdeArgs& a) {
   a.ctr_off = d->counter_offset;
   a.noise = d->d_noise;
   a.shift_u = d->d_shift_u;
-  {
-    const char* r = ab_env("PDEINV_SIM_REMAP");  // A/B switch for tools/sim_alloc.py
-    a.remap = r ? atoi(r) : 1;
-  }
   const pdeinv_potential& p = d->potential;
   int n_params = 0;
   switch (p.kind) {

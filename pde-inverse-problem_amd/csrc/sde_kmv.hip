@@ -1,12 +1,12 @@
 // sde_kmv.hip — the McKean–Vlasov simulator fused with the KMV residual's per-time-stamp sums (gfx950).
 #include "sde_common.h"
 
-using namespace pdeinv;
+namespace pdeinv {
 
 // ---- McKean–Vlasov simulate + the KMV residual's per-time-stamp sums (ABI 10) -----------------------------
 // The quadratic-Phi KMV residual (kinetic_mckean_vlasov.py:11-120, kmv.hip) reads, per time stamp t = trajectory
 // row t, [count, sum z, sum z z^T] of z = [x, v] and the d_s log rho-weighted [sum w, sum w x, sum w x x^T] of x
-// (w = d_s^2 log rho + (d_s log rho)^2 + gamma d_s log rho, kinetic_mckean_vlasov.py:243-248). The simulator stages
+// (w = d_s^2 log rho + (d_s log rho)^2 + gamma d_s log rho, kinetic_mckean_vlasov.py:86-91). The simulator stages
 // each wave's 64 rows of update t in LDS for its coalesced store anyway; here the same staged rows feed two
 // v_mfma_f32_16x16x4_f32 products over K = the wave's rows, once per update:
 //   P1 = Z^T Z                            the Gram of z (features zero-padded to 16)
@@ -100,18 +100,16 @@ __device__ __forceinline__ int kmv_tile_word(int e) {
   return p * 256 + (((i >> 2) * 16 + j) * 4 + (i & 3));
 }
 
-#ifndef PDEINV_MF_KMV_MINW
-#define PDEINV_MF_KMV_MINW 1
-#endif
+constexpr int kMfKmvMinWaves = 1;  // minimum waves per EU asked of the compiler
 template <int D, int WAVES, bool NXT>
-__global__ __launch_bounds__(64 * WAVES, PDEINV_MF_KMV_MINW) void sde_mf_kmv_kernel(
+__global__ __launch_bounds__(64 * WAVES, kMfKmvMinWaves) void sde_mf_kmv_kernel(
     SdeArgs a, const float* __restrict__ z0, float* __restrict__ traj, float* __restrict__ tau,
     float* __restrict__ last, KmvStamps ks, MfNext nx) {
   constexpr int M = 2 * D, B = 64 * WAVES, NCP = kmv_ncp<D>();
   constexpr int LZ = moment_len(M), LW = moment_len(D), LT = LZ + LW, kRed = (LT + B - 1) / B;
   static_assert(D % 2 == 0 && D <= 8, "even dim <= 8: 16-byte staged rows, a 16-feature Gram");
   const int nb = gridDim.x;
-  const int bid = a.remap ? xcd_block(blockIdx.x, nb) : (int)blockIdx.x;
+  const int bid = xcd_block(blockIdx.x, nb);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t i_raw = (int64_t)bid * B + threadIdx.x;
   const bool active = i_raw < a.N;
@@ -322,10 +320,8 @@ __global__ __launch_bounds__(64 * WAVES, PDEINV_MF_KMV_MINW) void sde_mf_kmv_ker
   }
 }
 
-#ifndef PDEINV_MF_KMV_WAVES
-#define PDEINV_MF_KMV_WAVES 4  // waves per block of sde_mf_kmv_kernel (the stamp partials shrink with the block)
-#endif
-constexpr int kMfKmvBlock = 64 * PDEINV_MF_KMV_WAVES;
+constexpr int kMfKmvWaves = 4;  // waves per block of sde_mf_kmv_kernel (the stamp partials shrink with the block)
+constexpr int kMfKmvBlock = 64 * kMfKmvWaves;
 
 static int mf_kmv_grid(int64_t N) { return (int)((N + kMfKmvBlock - 1) / kMfKmvBlock); }
 
@@ -345,6 +341,10 @@ static size_t mf_kmv_parts(const pdeinv_sde_desc* d, bool nxt, size_t off[4]) {
   return off[3] + (nxt ? pdeinv_mf_sums_workspace_bytes(d) : 0);
 }
 
+}  // namespace pdeinv
+
+using namespace pdeinv;
+
 extern "C" size_t pdeinv_sde_simulate_mf_kmv_workspace_bytes(const pdeinv_sde_desc* d, int32_t with_next) {
   if (!d || d->dim < 2 || d->dim > 8 || d->dim % 2 || d->n_particles <= 0 || d->n_steps < 1) return 0;
   size_t off[4];
@@ -355,7 +355,7 @@ template <int D, bool NXT>
 static void launch_mf_kmv(const SdeArgs& a, const float* z0, float* traj, float* tau, float* last, const float* coef,
                           const KmvStamps& ks, const MfNext& nx, hipStream_t st) {
   hipLaunchKernelGGL(kmv_coef_pairs_kernel<D>, dim3((unsigned)a.n_steps), dim3(128), 0, st, coef, const_cast<float*>(ks.cp));
-  hipLaunchKernelGGL((sde_mf_kmv_kernel<D, PDEINV_MF_KMV_WAVES, NXT>), dim3(mf_kmv_grid(a.N)), dim3(kMfKmvBlock), 0,
+  hipLaunchKernelGGL((sde_mf_kmv_kernel<D, kMfKmvWaves, NXT>), dim3(mf_kmv_grid(a.N)), dim3(kMfKmvBlock), 0,
                      st, a, z0, traj, tau, last, ks, nx);
 }
 

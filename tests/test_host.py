@@ -221,6 +221,26 @@ def test_library_exports_every_header_symbol():
     assert lib.pdeinv_moment_len(8) == 45 and lib.pdeinv_abi_version() == native.ABI_VERSION == 10
 
 
+def test_library_reads_no_environment_variable():
+    """a variable in the caller's shell cannot change which kernels run. The library has no
+    A/B knobs, so getenv / secure_getenv are not among its undefined dynamic symbols."""
+    import shutil
+    import subprocess
+    from utils import native
+    if not os.path.exists(native.LIB_PATH):
+        native.build()
+    if shutil.which("nm"):
+        cmd = ["nm", "-D", "--undefined-only", native.LIB_PATH]
+    else:
+        cmd = [os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "llvm-readelf"), "--dyn-syms",
+               native.LIB_PATH]
+    rows = [ln.split() for ln in subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.splitlines()]
+    # nm: "U name@VERSION"; readelf: "... NDX name@VERSION" with NDX = UND for an undefined symbol
+    undefined = {r[-1].split("@")[0] for r in rows if len(r) >= 2 and (r[-2] == "U" or "UND" in r)}
+    assert "malloc" in undefined or "memcpy" in undefined or "dlopen" in undefined, sorted(undefined)[:20]
+    assert not undefined & {"getenv", "secure_getenv"}
+
+
 def test_loader_fails_loudly_without_gpu():
     import torch
     from utils import native

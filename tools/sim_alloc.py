@@ -47,16 +47,10 @@ def block(b, reps=20, mom=True):
 
 for b in sets:  # warm every set once
     block(b, 3)
-variants = os.environ.get("SIM_ALLOC_VARIANTS", "")  # e.g. "PDEINV_SIM_REMAP=0,PDEINV_SIM_REMAP=1"
-variants = [v.split("=") for v in variants.split(",")] if variants else [None]
 for rnd in range(3):
     for k, b in enumerate(sets):
-        for var in variants:
-            if var:
-                os.environ[var[0]] = var[1]
-            t = block(b)
-            tr, ta = b["traj"].data_ptr(), b["tau"].data_ptr()
-            tag = "=".join(var) if var else ""
-            print(f"round {rnd} set {k} {tag}: {t:.4f} ms ({byt / t / 1e6:.0f} GB/s)  traj {tr:#x} "
-                  f"(mod2M {tr % (1 << 21):#x}, mod64M {tr % (1 << 26):#x})  tau {ta:#x} (mod2M {ta % (1 << 21):#x})",
-                  flush=True)
+        t = block(b)
+        tr, ta = b["traj"].data_ptr(), b["tau"].data_ptr()
+        print(f"round {rnd} set {k}: {t:.4f} ms ({byt / t / 1e6:.0f} GB/s)  traj {tr:#x} "
+              f"(mod2M {tr % (1 << 21):#x}, mod64M {tr % (1 << 26):#x})  tau {ta:#x} (mod2M {ta % (1 << 21):#x})",
+              flush=True)

@@ -1,5 +1,5 @@
 """Time the C2 simulator launch (d=4 KOU, 2^21 particles, n=100) with and without fused moments;
-one line per call. Used with PDEINV_SIM_LDS_PAD (occupancy study) and PDEINV_LIBRARY (A/B builds)."""
+one line per call. Used with PDEINV_LIBRARY (A/B builds)."""
 import os
 import sys
 
@@ -39,4 +39,4 @@ out = []
 for mom in (True, False):
     ms = bench(lambda: native.sde_simulate(z0, n, 0.02, 1.0, pot, seed=1, out=bufs, traj=True, tau=True, moments=mom))
     out.append(f"mom={int(mom)} {ms:.4f} ms {byt / ms / 1e6:.0f} GB/s")
-print(f"pad={os.environ.get('PDEINV_SIM_LDS_PAD', '0')} N={N} " + " | ".join(out), flush=True)
+print(f"N={N} " + " | ".join(out), flush=True)
