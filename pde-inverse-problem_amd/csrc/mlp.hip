@@ -1,4 +1,4 @@
-// mlp.hip — KFP residual for the non-parametric hypothesis V_hypothesis (gfx950).
+// mlp.hip — host drivers of the residuals for the non-parametric hypothesis V_hypothesis (gfx950).
 //
 // V(x) = sum_o y_o^2, y = h_L K_o + b_o, h_l = tanh(h_{l-1} K_l + b_l), h_0 = x   (core/model.py:32-62)
 // Per sample the residual (kinetic_fokker_planck.py:33-58) needs g = grad_x V, V' = g.v and
@@ -10,272 +10,24 @@
 //   F2  forward-mode adjoint of that chain (abar_l, zetabar_l)                      1P
 //   R2  reverse over the three forward streams                                      3P
 //   G   weight gradients: sums of outer products over samples (4 stream pairs)      4P
-// (24P FLOP per sample). The GEMMs are plain library GEMMs (rocBLAS sgemm, fp32
-// on the MFMA f32 path); every element-wise step, the per-row loss terms and the reductions are
-// the kernels below. The derivation is oracle/numpy_ref.py kfp_mlp_grad_analytic, checked against
-// central finite differences.
-#include <dlfcn.h>
-
-#include <atomic>
+// (24P FLOP per sample). The derivation is oracle/numpy_ref.py kfp_mlp_grad_analytic, checked
+// against central finite differences.
+//
+// That chain is run on blocks of rows by a row engine (mlp_engine.h): the hand-written fp32-MFMA kernels of
+// mlp_fused.hip for every AUTO / FUSED shape (FusedEngine below: shape envelope, zero padding, workspace), or
+// rocBLAS GEMMs for the opt-in cross-check impl = LIBRARY (mlp_library.hip). This file holds what both share and
+// what sits above them:
+//   - the per-row loss kernel mlp_loss<D> and its one launch table (launch_mlp_loss)
+//   - pdeinv_residual_kfp_mlp: three sample sets x chunks through the engine (config C5)
+//   - pdeinv_residual_kmv_mlp: the general-Phi KMV residual, as pair rows through the engine (kmv_rows_run) or
+//     through the narrow-net pair kernels of mlp_pairs.hip (kmv_pairs_orchestrate)
 #include <math.h>
-#include <rocblas/rocblas.h>
-
-#include <mutex>
 
 #include "common.h"
+#include "mlp_engine.h"
 #include "mlp_fused.h"
 
 namespace pdeinv {
-
-// ---- rocBLAS plumbing ------------------------------------------------------------------------
-// rocBLAS serves only the explicit opt-in impl = LIBRARY (a cross-check of the hand-written kernels): every AUTO /
-// FUSED shape runs on this library's own kernels. So libpdeinv.so does not link it: the first LIBRARY call loads
-// librocblas.so.5 with dlopen and resolves the five entry points it uses; without it that call fails loudly
-// (PDEINV_ERR_UNSUPPORTED), and no other path notices. (rocblas.h supplies the types only.)
-struct BlasApi {
-  decltype(&rocblas_create_handle) create_handle = nullptr;
-  decltype(&rocblas_destroy_handle) destroy_handle = nullptr;
-  decltype(&rocblas_set_stream) set_stream = nullptr;
-  decltype(&rocblas_sgemm) sgemm = nullptr;
-  decltype(&rocblas_sgemm_strided_batched) sgemm_strided_batched = nullptr;
-  bool ok = false;
-};
-
-// residual calls served by rocBLAS in this process (pdeinv_rocblas_calls: AUTO / FUSED never add to it)
-static std::atomic<int64_t> g_rocblas_calls{0};
-
-static const BlasApi& blas_api() {
-  static const BlasApi api = [] {
-    BlasApi a{};
-    void* lib = nullptr;
-    for (const char* name : {"librocblas.so.5", "/opt/rocm/lib/librocblas.so.5", "librocblas.so"}) {
-      lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-      if (lib) break;
-    }
-    if (!lib) return a;
-    a.create_handle = (decltype(a.create_handle))dlsym(lib, "rocblas_create_handle");
-    a.destroy_handle = (decltype(a.destroy_handle))dlsym(lib, "rocblas_destroy_handle");
-    a.set_stream = (decltype(a.set_stream))dlsym(lib, "rocblas_set_stream");
-    a.sgemm = (decltype(a.sgemm))dlsym(lib, "rocblas_sgemm");
-    a.sgemm_strided_batched = (decltype(a.sgemm_strided_batched))dlsym(lib, "rocblas_sgemm_strided_batched");
-    a.ok = a.create_handle && a.destroy_handle && a.set_stream && a.sgemm && a.sgemm_strided_batched;
-    return a;
-  }();
-  return api;
-}
-
-// One handle per (host thread, device): a rocBLAS handle carries its stream, so a handle shared
-// between threads lets one thread's rocblas_set_stream retarget another thread's GEMMs (the ABI
-// promises reentrancy across distinct streams, include/pdeinv.h). Thread-local handles need no lock
-// around set_stream + the GEMM sequence; they are destroyed when the thread exits.
-struct ThreadBlasHandles {
-  rocblas_handle h[64] = {};
-  ~ThreadBlasHandles() {
-    for (rocblas_handle& x : h)
-      if (x) blas_api().destroy_handle(x);
-  }
-};
-
-static rocblas_handle blas_handle(int device) {
-  thread_local ThreadBlasHandles handles;
-  if (device < 0 || device >= 64 || !blas_api().ok) return nullptr;
-  if (!handles.h[device]) {
-    if (blas_api().create_handle(&handles.h[device]) != rocblas_status_success) handles.h[device] = nullptr;
-  }
-  return handles.h[device];
-}
-
-// K-split factor of the weight-gradient GEMMs: the reduction runs over 4 x chunk rows while the
-// output is only n_in x n_out (<= 256 x 256), so one GEMM launches a few dozen workgroups. Slicing
-// the rows into up to kMaxKSplit batched GEMMs (>= kMinKSlice rows each) fills the chip; the fp32
-// partial slabs are summed in a fixed order (deterministic, no atomics).
-constexpr int kMaxKSplit = 256;
-constexpr int64_t kMinKSlice = 4096;
-constexpr int kColsumBlocks = 512;
-
-// out[i] += sum_k part[k * n + i]. A block owns kSumCols outputs; its kBlock / kSumCols thread
-// groups each sum a strided subset of the S slices (independent loads in flight), then the group
-// partials are added in a fixed order through LDS — deterministic, and fast for the small n
-// (a few thousand weights) and large S of the weight / bias gradients.
-constexpr int kSumCols = 32;
-__global__ __launch_bounds__(kBlock) void sum_slices_kernel(const float* __restrict__ part, int S, int64_t n,
-                                                            float* __restrict__ out) {
-  constexpr int G = kBlock / kSumCols;
-  __shared__ float red[G][kSumCols];
-  const int c = threadIdx.x % kSumCols, g = threadIdx.x / kSumCols;
-  const int64_t i = (int64_t)blockIdx.x * kSumCols + c;
-  float s = 0.f;
-  if (i < n)
-    for (int k = g; k < S; k += G) s += part[(int64_t)k * n + i];
-  red[g][c] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    float t = 0.f;
-#pragma unroll
-    for (int q = 0; q < G; ++q) t += red[q][c];
-    out[i] += t;
-  }
-}
-
-// partial column sums of B[R x n] (row-major): block b sums rows [b*rpb, (b+1)*rpb). For n < kBlock
-// the block's threads cover kBlock / n rows at a time (lane t: column t % n, row offset t / n), so
-// every thread is busy and a wave reads contiguous bytes; the row-lanes are combined in a fixed
-// order through LDS. Wider outputs use blockIdx.y column tiles of kBlock.
-__global__ __launch_bounds__(kBlock) void colsum_partial_kernel(const float* __restrict__ B, int64_t R, int n,
-                                                                int64_t rpb, float* __restrict__ part) {
-  __shared__ float red[kBlock];
-  const int64_t r0 = (int64_t)blockIdx.x * rpb;
-  const int64_t r1 = r0 + rpb < R ? r0 + rpb : R;
-  if (n >= kBlock) {
-    const int c = blockIdx.y * kBlock + threadIdx.x;
-    if (c >= n) return;
-    float s = 0.f;
-    for (int64_t r = r0; r < r1; ++r) s += B[r * n + c];
-    part[(int64_t)blockIdx.x * n + c] = s;
-    return;
-  }
-  const int lanes = kBlock / n;  // row-lanes (>= 1)
-  const int c = threadIdx.x % n, q = threadIdx.x / n;
-  float s = 0.f;
-  if (q < lanes)
-    for (int64_t r = r0 + q; r < r1; r += lanes) s += B[r * n + c];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  if (q == 0) {
-    float t = 0.f;
-    for (int k = 0; k < lanes; ++k) t += red[k * n + c];
-    part[(int64_t)blockIdx.x * n + c] = t;
-  }
-}
-
-struct Blas {
-  rocblas_handle h;
-  hipStream_t st;
-  float* part;  // >= kMaxKSplit * max(n_in * n_out) floats (also holds the colsum partials)
-  int status = 0;
-  // row-major C[R x n_out] = A[R x n_in] . K[n_in x n_out]
-  void fwd(const float* A, const float* K, float* C, int64_t R, int n_in, int n_out) {
-    const float one = 1.f, zero = 0.f;
-    if (blas_api().sgemm(h, rocblas_operation_none, rocblas_operation_none, n_out, (rocblas_int)R, n_in, &one, K,
-                      n_out, A, n_in, &zero, C, n_out) != rocblas_status_success)
-      status = 1;
-  }
-  // row-major C[R x n_in] = A[R x n_out] . K^T
-  void bwd(const float* A, const float* K, float* C, int64_t R, int n_in, int n_out) {
-    const float one = 1.f, zero = 0.f;
-    if (blas_api().sgemm(h, rocblas_operation_transpose, rocblas_operation_none, n_in, (rocblas_int)R, n_out, &one, K,
-                      n_out, A, n_out, &zero, C, n_in) != rocblas_status_success)
-      status = 1;
-  }
-  // Kbar[n_in x n_out] += A[R x n_in]^T . B[R x n_out]  (K-split into S batched slices + slab sum)
-  void wgrad(const float* A, const float* B, float* Kbar, int64_t R, int n_in, int n_out) {
-    const float one = 1.f, zero = 0.f;
-    int64_t S = R / kMinKSlice;
-    S = S < 1 ? 1 : (S > kMaxKSplit ? kMaxKSplit : S);
-    const int64_t Ks = R / S, rem = R - S * Ks;
-    const int64_t nout = (int64_t)n_in * n_out;
-    if (blas_api().sgemm_strided_batched(h, rocblas_operation_none, rocblas_operation_transpose, n_out, n_in,
-                                      (rocblas_int)Ks, &one, B, n_out, Ks * n_out, A, n_in, Ks * n_in, &zero, part,
-                                      n_out, nout, (rocblas_int)S) != rocblas_status_success)
-      status = 1;
-    hipLaunchKernelGGL(sum_slices_kernel, dim3(grid_for(nout, kSumCols)), dim3(kBlock), 0, st, part, (int)S, nout, Kbar);
-    if (rem > 0 && blas_api().sgemm(h, rocblas_operation_none, rocblas_operation_transpose, n_out, n_in,
-                                 (rocblas_int)rem, &one, B + S * Ks * n_out, n_out, A + S * Ks * n_in, n_in, &one,
-                                 Kbar, n_out) != rocblas_status_success)
-      status = 1;
-  }
-  // bbar[n] += sum over the R rows of B[R x n]
-  void colsum(const float* B, float* bbar, int64_t R, int n) {
-    const int64_t rpb = (R + kColsumBlocks - 1) / kColsumBlocks;
-    const int nb = (int)((R + rpb - 1) / rpb);
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3(nb, n >= kBlock ? (n + kBlock - 1) / kBlock : 1), dim3(kBlock), 0,
-                       st, B, R, n, rpb, part);
-    hipLaunchKernelGGL(sum_slices_kernel, dim3(grid_for(n, kSumCols)), dim3(kBlock), 0, st, part, nb, (int64_t)n, bbar);
-  }
-};
-
-// ---- element-wise kernels --------------------------------------------------------------------
-__device__ __forceinline__ float fast_tanh(float z) {
-  // tanh(z) = 1 - 2 / (exp(2z) + 1); exp2 on the hardware unit, saturates cleanly at +-1
-  const float e = __builtin_amdgcn_exp2f(2.8853900817779268f * z);
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-// F1: z (+bias), z', z'' -> h = tanh z, h' = s1 z', h'' = s1 z'' + s2 z'^2
-__global__ void mlp_act_fwd(const float* __restrict__ Z, float* __restrict__ A, const float* __restrict__ bias,
-                            int64_t R, int n) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t S = R * n;
-  if (e >= S) return;
-  const int j = (int)(e % n);
-  const float z = Z[e] + bias[j], zd = Z[S + e], zdd = Z[2 * S + e];
-  const float h = fast_tanh(z);
-  const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-  A[e] = h;
-  A[S + e] = s1 * zd;
-  A[2 * S + e] = fmaf(s1, zdd, s2 * zd * zd);
-}
-
-// output layer: y (+bias) stored back; u = 2y (seed of the grad_x chain); per row
-// terms = {V' = 2 y.y', V'' = 2(y'.y' + y.y''), V = y.y, 0}
-// A block owns rb consecutive rows = rb*O consecutive elements of each plane: phase 1 is
-// element-wise and coalesced, the per-element products go to LDS, phase 2 sums them per row.
-__global__ __launch_bounds__(kBlock) void mlp_out(float* __restrict__ Y, const float* __restrict__ bias,
-                                                  float* __restrict__ YB, float4* __restrict__ terms, int64_t R,
-                                                  int O, int rb) {
-  extern __shared__ float prod[];  // [3][rb*O]
-  const int64_t S = R * O;
-  const int64_t r0 = (int64_t)blockIdx.x * rb;
-  const int nr = (int)((R - r0) < rb ? (R - r0) : rb);
-  const int ne = nr * O;
-  const int64_t e0 = r0 * O;
-  for (int k = threadIdx.x; k < ne; k += kBlock) {
-    const int64_t e = e0 + k;
-    const float y = Y[e] + bias[k % O], yd = Y[S + e], ydd = Y[2 * S + e];
-    Y[e] = y;
-    YB[3 * S + e] = 2.f * y;
-    prod[k] = y * yd;
-    prod[rb * O + k] = fmaf(yd, yd, y * ydd);
-    prod[2 * rb * O + k] = y * y;
-  }
-  __syncthreads();
-  for (int r = threadIdx.x; r < nr; r += kBlock) {
-    float vd = 0.f, vdd = 0.f, v = 0.f;
-    for (int o = 0; o < O; ++o) {
-      vd += prod[r * O + o];
-      vdd += prod[rb * O + r * O + o];
-      v += prod[2 * rb * O + r * O + o];
-    }
-    terms[r0 + r] = make_float4(2.f * vd, 2.f * vdd, v, 0.f);
-  }
-}
-
-// R1: zeta = tanh'(z) * a   (a = GEMM output, kept for R2)
-__global__ void mlp_gchain(const float* __restrict__ a, const float* __restrict__ h, float* __restrict__ zeta,
-                           int64_t S) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= S) return;
-  const float hv = h[e];
-  zeta[e] = (1.f - hv * hv) * a[e];
-}
-
-// F2: abar = tanh'(z) * zetabar
-__global__ void mlp_gadj(const float* __restrict__ zetabar, const float* __restrict__ h, float* __restrict__ abar,
-                         int64_t S) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= S) return;
-  const float hv = h[e];
-  abar[e] = (1.f - hv * hv) * zetabar[e];
-}
-
-struct MlpLossArgs {
-  int d, set, true_kind, KT, bval;
-  int uw;  // rows carry [x | v | u | w]: input-gradient seed u (added to abar_0) and value weight w
-           // (KMV pair rows, set 3: pdeinv_residual_kmv_mlp)
-  float c1, c2, c3, c0, c_true, inv_n;
-  float s2t, l2st;
-  float tp[PDEINV_MAX_PARAMS];  // tilde_F [d*d] or true GMM centres [K*d]
-};
 
 // per row: T1 = |g|^2, T2 = V'', T3 = V', T0 = V, true-potential terms (0T rows); seeds
 // abar_0 = 2 c1 g; block partial sums of the 8 accumulator slots of pdeinv.h (PDEINV_GMM_ACC_*).
@@ -366,47 +118,6 @@ __global__ __launch_bounds__(kBlock) void mlp_loss(MlpLossArgs a, const float* _
   block_reduce_to_slab(acc, PDEINV_GMM_NACC, lds, partials, blockIdx.x, gridDim.x);
 }
 
-// seeds of the reverse sweep over the forward streams (c0: weight of the value V = y.y):
-//   ybar = 2 c3 y' + 2 c2 y'' + 2 ubar + 2 c0 y,  y'bar = 2 c3 y + 4 c2 y',  y''bar = 2 c2 y
-// (rw: optional per-row weight of the value term, rw[r * ldw] for element e = r * O + o)
-__global__ void mlp_seeds(const float* __restrict__ Y, const float* __restrict__ UB, float* __restrict__ YB,
-                          float c2, float c3, float c0, int64_t S, const float* __restrict__ rw, int64_t ldw, int O) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= S) return;
-  const float y = Y[e], yd = Y[S + e], ydd = Y[2 * S + e];
-  const float cv = rw ? c0 * rw[(e / O) * ldw] : c0;
-  YB[e] = 2.f * c3 * yd + 2.f * c2 * ydd + 2.f * UB[e] + 2.f * cv * y;
-  YB[S + e] = 2.f * c3 * y + 4.f * c2 * yd;
-  YB[2 * S + e] = 2.f * c2 * y;
-}
-
-// R2 element-wise step through tanh (s1 = tanh', s2 = tanh'', s3 = tanh'''):
-//   zbar   = s1 hbar + s2 z' h'bar + (s2 z'' + s3 z'^2) h''bar + s2 a zetabar   (last: grad_x chain)
-//   z'bar  = s1 h'bar + 2 s2 z' h''bar ;   z''bar = s1 h''bar
-__global__ void mlp_act_bwd(const float* __restrict__ HB, const float* __restrict__ h, const float* __restrict__ Z,
-                            const float* __restrict__ aL, const float* __restrict__ zb, float* __restrict__ ZB,
-                            int64_t S) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= S) return;
-  const float hv = h[e];
-  const float s1 = 1.f - hv * hv, s2 = -2.f * hv * s1, s3 = -2.f * s1 * s1 - 2.f * hv * s2;
-  const float zd = Z[S + e], zdd = Z[2 * S + e];
-  const float hb = HB[e], hdb = HB[S + e], hddb = HB[2 * S + e];
-  ZB[e] = s1 * hb + s2 * zd * hdb + (s2 * zdd + s3 * zd * zd) * hddb + s2 * aL[e] * zb[e];
-  ZB[S + e] = s1 * hdb + 2.f * s2 * zd * hddb;
-  ZB[2 * S + e] = s1 * hddb;
-}
-
-// copy the (x, v) rows of a sample set into the stream-0 / stream-1 input planes of layer 1
-__global__ void mlp_load_rows(const float* __restrict__ z, int64_t ld, int d, float* __restrict__ A0, int64_t R) {
-  const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (e >= R * d) return;
-  const int64_t r = e / d;
-  const int i = (int)(e - r * d);
-  A0[e] = z[r * ld + i];
-  A0[R * d + e] = z[r * ld + d + i];
-}
-
 __global__ void slab_reduce_accum_kernel(const float* __restrict__ partials, int n_blocks,
                                          double* __restrict__ out) {
   const int c = blockIdx.x;
@@ -443,42 +154,26 @@ __global__ void kfp_terms_finalize_kernel(const double* __restrict__ acc, const 
   }
 }
 
-// ---- workspace plan -------------------------------------------------------------------------
-constexpr int kLossGrid = 512;
-
-struct MlpPlan {
-  int d, L, W, O;
-  int64_t Bc;
-  size_t off_A0, off_Y, off_YB, off_UB, off_G, off_kpart, off_terms, off_part, total;
-  size_t off_layer0, layer_stride;  // per hidden layer: A(4) Z(3) ZB(4) HB(3) aL(1) zb(1) planes of Bc*W
-};
-
-static MlpPlan make_plan(const pdeinv_kfp_mlp_desc* d) {
-  MlpPlan p{};
-  p.d = d->dim; p.L = d->n_layers; p.W = d->width; p.O = d->out_features;
-  p.Bc = d->chunk_rows > 0 ? d->chunk_rows : (1 << 18);
-  size_t o = 0;
-  auto take = [&](size_t floats) { const size_t at = o; o += (floats + 63) & ~(size_t)63; return at; };
-  p.off_A0 = take(4 * p.Bc * p.d);
-  p.off_Y = take(3 * p.Bc * p.O);
-  p.off_YB = take(4 * p.Bc * p.O);
-  p.off_UB = take(p.Bc * p.O);
-  p.off_G = take(p.Bc * p.d);
-  const int64_t wmax = (int64_t)p.W * (p.W > p.d ? (p.W > p.O ? p.W : p.O) : p.d);
-  const int64_t cmax = (int64_t)kColsumBlocks * (p.W > p.O ? p.W : p.O);
-  p.off_kpart = take((size_t)(kMaxKSplit * wmax > cmax ? kMaxKSplit * wmax : cmax));
-  p.off_terms = take(4 * p.Bc);
-  p.off_part = take((size_t)PDEINV_GMM_NACC * kLossGrid);
-  p.layer_stride = 16 * p.Bc * p.W;
-  p.off_layer0 = take(p.layer_stride * p.L);
-  p.total = o * sizeof(float);
-  return p;
+// The one launch table of mlp_loss: the fused engine's dims (2, 4, 8, 16) and the library engine's (1-8, 10, 12, 16).
+int launch_mlp_loss(const MlpLossArgs& la, const float* G, const float* X, int64_t ldx, const float4* terms,
+                    float* abar0, int64_t R, float* part, double* acc, hipStream_t st) {
+  const int lg = grid_for(R) < kLossGrid ? grid_for(R) : kLossGrid;
+  switch (la.d) {
+#define CASE(DD) case DD: hipLaunchKernelGGL(mlp_loss<DD>, dim3(lg), dim3(kBlock), 0, st, la, G, X, ldx, terms, abar0, R, part); break;
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(10) CASE(12) CASE(16)
+#undef CASE
+    default:
+      return fail(PDEINV_ERR_UNSUPPORTED, "mlp: dim must be one of 1-8, 10, 12, 16");
+  }
+  hipLaunchKernelGGL(slab_reduce_accum_kernel, dim3(PDEINV_GMM_NACC), dim3(kBlock), 0, st, part, lg, acc);
+  return PDEINV_OK;
 }
 
 }  // namespace pdeinv
 
 using namespace pdeinv;
 
+// ---- the fused row engine ----------------------------------------------------------------------
 // The shapes the fused fp32-MFMA path takes. The kernels are compiled for dim in {2, 4, 8, 16} and width in
 // {32, 64, 128, 256, 512, 1024} (any depth 1..16, any out_features: mlpf::supported); every other dim <= 16 and
 // width <= 1024 runs zero-padded to the next compiled one — exact: padded inputs and K1 rows are zero, padded
@@ -505,17 +200,11 @@ static bool fused_shape(const pdeinv_kfp_mlp_desc* d, FusedShape* f = nullptr) {
 
 // The shape runs the hand-written fused fp32-MFMA path under impl = AUTO: the padded envelope of fused_shape (dims
 // and widths zero-padded to the compiled ones), not only the compiled shapes themselves.
-extern "C" int64_t pdeinv_rocblas_calls(void) { return g_rocblas_calls.load(std::memory_order_relaxed); }
-
 extern "C" int pdeinv_mlp_fused_supported(int32_t dim, int32_t n_layers, int32_t width, int32_t out_features) {
   pdeinv_kfp_mlp_desc d{};
   d.dim = dim; d.n_layers = n_layers; d.width = width; d.out_features = out_features;
   d.impl = PDEINV_MLP_IMPL_AUTO;
   return fused_shape(&d) ? 1 : 0;
-}
-
-static MlpPadMap width_pad_map(const pdeinv_kfp_mlp_desc* d, const FusedShape& f) {
-  return mlp_pad_map(d->dim, d->width, d->n_layers, d->out_features, f.Dp, f.Wp, d->out_features);
 }
 
 __global__ void mlp_pad_params_kernel(MlpPadMap pm, const float* __restrict__ src, int64_t P, float* __restrict__ dst) {
@@ -532,29 +221,6 @@ __global__ void mlp_unpad_grad_kernel(MlpPadMap pm, const float* __restrict__ gp
   if (r >= 0) grad[r] += gp[q];
 }
 
-static int64_t chunk_rows_of(const pdeinv_kfp_mlp_desc* d) { return d->chunk_rows > 0 ? d->chunk_rows : (1 << 18); }
-
-// fused-path workspace (floats): [run_chunk workspace | loss partials | padded params | padded gradient |
-// padded rows (dim padding)]
-struct FusedWs {
-  size_t fl, part, pbuf, gbuf, rows, total;
-  int64_t PP;
-};
-static FusedWs fused_ws(const pdeinv_kfp_mlp_desc* d, const FusedShape& f) {
-  FusedWs w{};
-  const int64_t Bc = chunk_rows_of(d);
-  size_t o = 0;
-  auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
-  w.fl = take(mlpf::workspace_floats(f.Dp, d->n_layers, f.Wp, d->out_features, Bc));
-  w.part = take((size_t)PDEINV_GMM_NACC * kLossGrid);
-  w.PP = f.pad ? width_pad_map(d, f).padded_count() : 0;
-  w.pbuf = take((size_t)w.PP);
-  w.gbuf = take((size_t)w.PP);
-  w.rows = take(f.Dp != d->dim ? (size_t)Bc * 2 * f.Dp : 0);
-  w.total = o;
-  return w;
-}
-
 // rows [x | v] of d floats -> [x, 0.. | v, 0..] of Dp (the fused path's dim padding)
 __global__ void mlp_pad_rows_kernel(const float* __restrict__ src, int64_t ld, int64_t R, int D, int Dp,
                                     float* __restrict__ dst) {
@@ -565,148 +231,136 @@ __global__ void mlp_pad_rows_kernel(const float* __restrict__ src, int64_t ld, i
   dst[q] = k < D ? src[r * ld + half * D + k] : 0.f;
 }
 
-extern "C" size_t pdeinv_residual_kfp_mlp_workspace_bytes(const pdeinv_kfp_mlp_desc* d) {
-  if (!d || d->dim < 1 || d->n_layers < 1 || d->width < 1 || d->out_features < 1) return 0;
-  FusedShape f;
-  if (fused_shape(d, &f)) return fused_ws(d, f).total * sizeof(float);
-  return make_plan(d).total;
-}
-
-namespace pdeinv {
+namespace {
 struct LossCtx {
-  MlpLossArgs la;
+  const MlpLossArgs* la;
   const float* zr;
   int64_t ld;
   float* part;
   double* acc;
-  int D;
 };
 
-static int fused_loss_hook(void* p, const float* G, const float4* terms, float* abar0, int64_t R, hipStream_t st) {
-  LossCtx* c = (LossCtx*)p;
-  const int lg = grid_for(R) < kLossGrid ? grid_for(R) : kLossGrid;
-  switch (c->D) {
-#define CASE(DD) case DD: hipLaunchKernelGGL(mlp_loss<DD>, dim3(lg), dim3(kBlock), 0, st, c->la, G, c->zr, c->ld, terms, abar0, R, c->part); break;
-    CASE(2) CASE(4) CASE(8) CASE(16)
-#undef CASE
-    default:
-      return fail(PDEINV_ERR_UNSUPPORTED, "kfp_mlp fused: dim must be 2, 4, 8 or 16");
-  }
-  hipLaunchKernelGGL(slab_reduce_accum_kernel, dim3(PDEINV_GMM_NACC), dim3(kBlock), 0, st, c->part, lg, c->acc);
-  return check_launch("kfp_mlp fused loss");
-}
-}  // namespace pdeinv
-
-namespace pdeinv {
-// parameter offsets (flax order: K_1, b_1, ..., K_L, b_L, K_o, b_o)
-static void param_offsets(int D, int W, int O, int L, int64_t* poff, int64_t* boff) {
-  int64_t o = 0;
-  for (int l = 0; l <= L; ++l) {
-    const int n_in = (l == 0) ? D : W, n_out = (l == L) ? O : W;
-    poff[l] = o; o += (int64_t)n_in * n_out;
-    boff[l] = o; o += n_out;
-  }
+int fused_loss_hook(void* p, const float* G, const float4* terms, float* abar0, int64_t R, hipStream_t st) {
+  const LossCtx* c = (const LossCtx*)p;
+  const int rc = launch_mlp_loss(*c->la, G, c->zr, c->ld, terms, abar0, R, c->part, c->acc, st);
+  return rc ? rc : check_launch("kfp_mlp fused loss");
 }
 
-// One chunk of R rows through the library path: F1 Taylor forward, R1 grad_x chain, the loss
-// terms (mlp_loss, accumulated into acc), F2 forward adjoint, R2 + weight gradients (accumulated
-// into grad). grad_only stops after R1 and leaves g = grad_x V of every row in G (KMV pass 1).
-struct LibRun {
-  MlpPlan p;
-  Blas* blas;
-  float* w;
-  const float* params;
-  float* grad;
-  const int64_t* poff;
-  const int64_t* boff;
-  hipStream_t st;
-  double* acc;
-  int64_t R = 0;
-  float* layer(int l, int plane) const {
-    return w + p.off_layer0 + p.layer_stride * (l - 1) + (size_t)plane * R * p.W;
+struct FusedEngine final : RowEngine {
+  const int D, L, O, Dp, Wp;
+  const int64_t Bc;
+  const bool pad;  // some dim or width is zero-padded: the chain runs on a padded parameter copy
+  const std::string who;
+  MlpPadMap pm{};
+  int64_t PP = 0;  // padded parameter count (0: no padding)
+  // workspace (floats): [run_chunk workspace | loss partials | padded params | padded gradient | padded rows]
+  size_t off_part, off_pbuf, off_gbuf, off_rows, total;
+  bool pad_rows;  // the caller's rows are [x | v] of D floats: copied to Dp per chunk
+  float* w = nullptr;
+  double* acc = nullptr;
+  float* grad_out = nullptr;
+  hipStream_t st = nullptr;
+  int64_t poff[18], boff[18];
+  mlpf::Chunk c{};
+
+  // rows_padded: the caller builds its rows with row_dim() coordinates per block (the KMV pair rows)
+  FusedEngine(const pdeinv_kfp_mlp_desc& m, const FusedShape& f, bool rows_padded, const char* who_)
+      : D(m.dim), L(m.n_layers), O(m.out_features), Dp(f.Dp), Wp(f.Wp), Bc(chunk_rows_of(&m)), pad(f.pad),
+        who(who_), pad_rows(!rows_padded && f.Dp != m.dim) {
+    if (pad) {
+      pm = mlp_pad_map(D, m.width, L, O, Dp, Wp, O);
+      PP = pm.padded_count();
+    }
+    size_t o = 0;
+    auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
+    take(mlpf::workspace_floats(Dp, L, Wp, O, Bc));
+    off_part = take((size_t)PDEINV_GMM_NACC * kLossGrid);
+    off_pbuf = take((size_t)PP);
+    off_gbuf = take((size_t)PP);
+    off_rows = take(pad_rows ? (size_t)Bc * 2 * Dp : 0);
+    total = o;
   }
-  float* G() const { return w + p.off_G; }
-  int chunk(const float* zr, int64_t ld, int64_t rows, const MlpLossArgs& la, bool grad_only) {
-    R = rows;
-    const int D = p.d, W = p.W, O = p.O, L = p.L;
-    float* A0 = w + p.off_A0;
-    float* Y = w + p.off_Y;
-    float* YB = w + p.off_YB;
-    float* UB = w + p.off_UB;
-    float* Gp = G();
-    float4* terms = (float4*)(w + p.off_terms);
-    float* part = w + p.off_part;
-    Blas& b = *blas;
-    // planes per hidden layer l: A 0-3, Z 4-6, ZB 7-10, HB 11-13, aL 14, zb 15. Inside a chunk of R
-    // rows the planes are packed at stride R*W so that consecutive streams form one [k*R x W] operand.
-    const int64_t SD = R * D, SW = R * W, SO = R * O;
-    // ---- F1: Taylor-mode forward --------------------------------------------------------
-    hipLaunchKernelGGL(mlp_load_rows, dim3(grid_for(SD)), dim3(kBlock), 0, st, zr, ld, D, A0, R);
-    if (hipMemsetAsync(A0 + 2 * SD, 0, sizeof(float) * SD, st) != hipSuccess) return fail(PDEINV_ERR_HIP, "memset");
-    for (int l = 1; l <= L; ++l) {
-      const int n_in = (l == 1) ? D : W;
-      const float* Ain = (l == 1) ? A0 : layer(l - 1, 0);
-      float* Z = layer(l, 4);
-      b.fwd(Ain, params + poff[l - 1], Z, 3 * R, n_in, W);  // three streams: one GEMM with 3R rows
-      hipLaunchKernelGGL(mlp_act_fwd, dim3(grid_for(SW)), dim3(kBlock), 0, st, Z, layer(l, 0), params + boff[l - 1],
-                         R, W);
+  int row_dim() const override { return Dp; }
+  size_t ws_floats() const override { return total; }
+  const float* grad_rows() const override { return mlpf::grad_rows(c); }
+
+  int begin(const float* params, float* grad, float* ws, double* acc_, hipStream_t st_) override {
+    w = ws; acc = acc_; grad_out = grad; st = st_;
+    param_offsets(Dp, Wp, O, L, poff, boff);
+    c = mlpf::Chunk{};
+    c.d = Dp; c.L = L; c.W = Wp; c.O = O;
+    c.params = params; c.grad = grad; c.poff = poff; c.boff = boff;
+    c.ws = w; c.Bc = Bc;
+    if (pad) {  // zero-padded copy of the parameters and a padded gradient accumulator behind the workspace
+      float* pbuf = w + off_pbuf;
+      float* gbuf = w + off_gbuf;
+      hipLaunchKernelGGL(mlp_pad_params_kernel, dim3((unsigned)((PP + 255) / 256)), dim3(256), 0, st, pm, params, PP,
+                         pbuf);
+      if (hipMemsetAsync(gbuf, 0, sizeof(float) * PP, st) != hipSuccess) return fail(PDEINV_ERR_HIP, who + ": memset");
+      c.params = pbuf;
+      c.grad = gbuf;
     }
-    b.fwd(layer(L, 0), params + poff[L], Y, 3 * R, W, O);
-    {
-      const int rb = O >= 2048 ? 1 : 2048 / O;  // 24 KB of LDS products per block
-      hipLaunchKernelGGL(mlp_out, dim3((unsigned)((R + rb - 1) / rb)), dim3(kBlock), 3 * rb * O * sizeof(float), st,
-                         Y, params + boff[L], YB, terms, R, O, rb);
+    return PDEINV_OK;
+  }
+
+  int chunk(const float* rows, int64_t ld, int64_t R, const MlpLossArgs& la, RowMode mode,
+            const float* wrow) override {
+    c.R = R;
+    c.z = rows;
+    c.ldz = ld;
+    if (pad_rows) {
+      float* prow = w + off_rows;
+      const int64_t nq = R * 2 * Dp;
+      hipLaunchKernelGGL(mlp_pad_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, rows, ld, R, D, Dp,
+                         prow);
+      c.z = prow;
+      c.ldz = 2 * Dp;
     }
-    // ---- R1: grad_x chain ---------------------------------------------------------------
-    b.bwd(YB + 3 * SO, params + poff[L], layer(L, 14), R, W, O);  // a_L = u K_o^T
-    for (int l = L; l >= 1; --l) {
-      hipLaunchKernelGGL(mlp_gchain, dim3(grid_for(SW)), dim3(kBlock), 0, st, layer(l, 14), layer(l, 0),
-                         layer(l, 10), SW);  // zeta_l -> ZB plane 3
-      if (l > 1) b.bwd(layer(l, 10), params + poff[l - 1], layer(l - 1, 14), R, W, W);
-      else b.bwd(layer(1, 10), params + poff[0], Gp, R, D, W);  // g = zeta_1 K_1^T
-    }
-    if (grad_only) {
-      if (b.status) return fail(PDEINV_ERR_HIP, "mlp: rocBLAS call failed");
-      return check_launch("mlp grad_x kernels");
-    }
-    // ---- loss terms, seed abar_0 = 2 c1 g (+ u) ------------------------------------------
-    const int lg = grid_for(R) < kLossGrid ? grid_for(R) : kLossGrid;
-    switch (D) {
-#define CASE(DD) case DD: hipLaunchKernelGGL(mlp_loss<DD>, dim3(lg), dim3(kBlock), 0, st, la, Gp, zr, ld, terms, A0 + 3 * SD, R, part); break;
-      CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(10) CASE(12) CASE(16)
-#undef CASE
-      default:
-        return fail(PDEINV_ERR_UNSUPPORTED, "mlp: dim must be one of 1-8, 10, 12, 16");
-    }
-    hipLaunchKernelGGL(slab_reduce_accum_kernel, dim3(PDEINV_GMM_NACC), dim3(kBlock), 0, st, part, lg, acc);
-    // ---- F2: forward-mode adjoint of the grad_x chain --------------------------------------
-    for (int l = 1; l <= L; ++l) {
-      const float* abar_prev = (l == 1) ? A0 + 3 * SD : layer(l - 1, 3);
-      b.fwd(abar_prev, params + poff[l - 1], layer(l, 15), R, (l == 1) ? D : W, W);  // zetabar_l
-      hipLaunchKernelGGL(mlp_gadj, dim3(grid_for(SW)), dim3(kBlock), 0, st, layer(l, 15), layer(l, 0),
-                         layer(l, 3), SW);  // abar_l -> A plane 3
-    }
-    b.fwd(layer(L, 3), params + poff[L], UB, R, W, O);  // ubar = abar_L K_o
-    hipLaunchKernelGGL(mlp_seeds, dim3(grid_for(SO)), dim3(kBlock), 0, st, Y, UB, YB, la.c2, la.c3, la.c0, SO,
-                       la.uw ? zr + 3 * D : nullptr, ld, O);
-    // ---- R2 + G: reverse over the three forward streams, weight gradients ---------------------
-    b.wgrad(layer(L, 0), YB, grad + poff[L], 4 * R, W, O);  // K_o += [h;h';h'';abar]^T [ybar;..;u]
-    b.colsum(YB, grad + boff[L], R, O);
-    b.bwd(YB, params + poff[L], layer(L, 11), 3 * R, W, O);  // hbar streams of layer L
-    for (int l = L; l >= 1; --l) {
-      hipLaunchKernelGGL(mlp_act_bwd, dim3(grid_for(SW)), dim3(kBlock), 0, st, layer(l, 11), layer(l, 0),
-                         layer(l, 4), layer(l, 14), layer(l, 15), layer(l, 7), SW);
-      const int n_in = (l == 1) ? D : W;
-      const float* Ain = (l == 1) ? A0 : layer(l - 1, 0);
-      b.wgrad(Ain, layer(l, 7), grad + poff[l - 1], 4 * R, n_in, W);
-      b.colsum(layer(l, 7), grad + boff[l - 1], R, W);
-      if (l > 1) b.bwd(layer(l, 7), params + poff[l - 1], layer(l - 1, 11), 3 * R, W, W);
-    }
-    if (b.status) return fail(PDEINV_ERR_HIP, "mlp: rocBLAS call failed");
-    return check_launch("mlp kernels");
+    c.c2 = la.c2; c.c3 = la.c3; c.c0 = la.c0;
+    c.wrow = wrow;
+    c.ldw = wrow ? ld : 0;
+    c.grad_only = mode == RowMode::GRAD_ONLY;
+    c.first_order = mode == RowMode::FIRST_ORDER;
+    LossCtx lc{&la, c.z, c.ldz, w + off_part, acc};
+    return mlpf::run_chunk(c, mlpf::LossHook{fused_loss_hook, &lc}, st);
+  }
+
+  int end() override {
+    if (!pad) return PDEINV_OK;
+    hipLaunchKernelGGL(mlp_unpad_grad_kernel, dim3((unsigned)((PP + 255) / 256)), dim3(256), 0, st, pm, c.grad, PP,
+                       grad_out);
+    return check_launch("mlp_unpad_grad_kernel");
   }
 };
-}  // namespace pdeinv
+
+// The true potential of the 0T loss terms on rows of Dp > la.d coordinates: zero rows / columns of tilde_F, zero
+// coordinates of mu_k.
+int pad_true_potential(MlpLossArgs& la, int Dp) {
+  const int D = la.d;
+  if (Dp == D) return PDEINV_OK;
+  PDEINV_REQUIRE(la.true_kind == PDEINV_POT_QUADRATIC || la.KT * Dp <= PDEINV_MAX_PARAMS, PDEINV_ERR_UNSUPPORTED,
+                 "kfp_mlp: padded true GMM exceeds PDEINV_MAX_PARAMS");
+  const int rows = la.true_kind == PDEINV_POT_QUADRATIC ? D : la.KT;
+  float tp[PDEINV_MAX_PARAMS];
+  for (int k = 0; k < PDEINV_MAX_PARAMS; ++k) { tp[k] = la.tp[k]; la.tp[k] = 0.f; }
+  for (int k = 0; k < rows; ++k)
+    for (int i = 0; i < D; ++i) la.tp[k * Dp + i] = tp[k * D + i];
+  la.d = Dp;
+  return PDEINV_OK;
+}
+
+// the engine of a KFP descriptor: fused inside the envelope, else the library plan (only impl = LIBRARY runs it)
+std::unique_ptr<RowEngine> kfp_engine(const pdeinv_kfp_mlp_desc* d) {
+  FusedShape f;
+  if (fused_shape(d, &f)) return std::make_unique<FusedEngine>(*d, f, false, "kfp_mlp");
+  return make_library_engine(*d, "kfp_mlp");
+}
+}  // namespace
+
+extern "C" size_t pdeinv_residual_kfp_mlp_workspace_bytes(const pdeinv_kfp_mlp_desc* d) {
+  if (!d || d->dim < 1 || d->n_layers < 1 || d->width < 1 || d->out_features < 1) return 0;
+  return kfp_engine(d)->ws_floats() * sizeof(float);
+}
 
 extern "C" int64_t pdeinv_mlp_param_count(int32_t dim, int32_t n_layers, int32_t width, int32_t out_features) {
   int64_t n = (int64_t)dim * width + width;
@@ -714,6 +368,7 @@ extern "C" int64_t pdeinv_mlp_param_count(int32_t dim, int32_t n_layers, int32_t
   return n + (int64_t)width * out_features + out_features;
 }
 
+// ---- KFP residual (config C5) --------------------------------------------------------------------
 extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float* zi, int64_t ni, int64_t ldi,
                                        const float* zt, int64_t nt, int64_t ldt, const float* z0, int64_t n0,
                                        int64_t ld0, const float* params, void* ws, double* acc, float* grad,
@@ -738,16 +393,12 @@ extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float
   PDEINV_REQUIRE(d->impl == PDEINV_MLP_IMPL_LIBRARY || fused_shape(d), PDEINV_ERR_UNSUPPORTED,
                  "kfp_mlp: the hand-written path takes dim <= 16, 1 <= n_layers <= 16, width <= 1024 (zero-padded to "
                  "the compiled dims / widths), any out_features; impl = LIBRARY (rocBLAS) is the opt-in cross-check");
-  const MlpPlan p = make_plan(d);
-  PDEINV_REQUIRE(p.Bc <= (1 << 26), PDEINV_ERR_INVALID, "kfp_mlp: chunk_rows too large");
+  const int64_t Bc = chunk_rows_of(d);
+  PDEINV_REQUIRE(Bc <= (1 << 26), PDEINV_ERR_INVALID, "kfp_mlp: chunk_rows too large");
   hipStream_t st = (hipStream_t)stream;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return fail(PDEINV_ERR_HIP, "kfp_mlp: hipGetDevice failed");
-  float* w = (float*)ws;
-  const int W = p.W, O = p.O, L = p.L;
-  PDEINV_REQUIRE(L <= 16, PDEINV_ERR_UNSUPPORTED, "kfp_mlp: at most 16 hidden layers");
-  int64_t poff[18], boff[18];
-  param_offsets(D, W, O, L, poff, boff);
+  PDEINV_REQUIRE(d->n_layers <= 16, PDEINV_ERR_UNSUPPORTED, "kfp_mlp: at most 16 hidden layers");
 
   MlpLossArgs la{};
   la.d = D;
@@ -757,6 +408,7 @@ extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float
   la.l2st = la.s2t * 1.4426950408889634f;
   const int ntp = d->true_kind == PDEINV_POT_QUADRATIC ? D * D : d->n_centers_true * D;
   for (int k = 0; k < ntp; ++k) la.tp[k] = d->true_params[k];
+  la.c_true = d->c_true;
 
   // boundary sets weight V' (kinetic FP, :49-50) or V itself (overdamped FP, fokker_planck.py:48-52)
   const bool bval = d->boundary_value != 0;
@@ -765,99 +417,25 @@ extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float
       {z0, n0, ld0 ? ld0 : 2 * D, 0, d->c_nabla, d->c_hess, d->c_fric, 0.f},
       {zi, ni, ldi ? ldi : 2 * D, 1, 0.f, 0.f, bval ? 0.f : d->c_init, bval ? d->c_init : 0.f},
       {zt, nt, ldt ? ldt : 2 * D, 2, 0.f, 0.f, bval ? 0.f : d->c_term, bval ? d->c_term : 0.f}};
-  FusedShape fs;
-  if (fused_shape(d, &fs)) {
-    const int64_t Bc = chunk_rows_of(d);
-    const int Wf = fs.Wp, Dp = fs.Dp;
-    const FusedWs fw = fused_ws(d, fs);
-    float* wsf = (float*)ws;
-    const float* fparams = params;
-    float* fgrad = grad;
-    MlpPadMap pm{};
-    if (fs.pad) {  // zero-padded copy of the parameters and a padded gradient accumulator behind the workspace
-      pm = width_pad_map(d, fs);
-      float* pbuf = wsf + fw.pbuf;
-      float* gbuf = wsf + fw.gbuf;
-      hipLaunchKernelGGL(mlp_pad_params_kernel, dim3((unsigned)((fw.PP + 255) / 256)), dim3(256), 0, st, pm, params,
-                         fw.PP, pbuf);
-      if (hipMemsetAsync(gbuf, 0, sizeof(float) * fw.PP, st) != hipSuccess)
-        return fail(PDEINV_ERR_HIP, "kfp_mlp: memset");
-      fparams = pbuf;
-      fgrad = gbuf;
-      param_offsets(Dp, Wf, O, L, poff, boff);
-    }
-    LossCtx lc{};
-    lc.la = la;
-    if (Dp != D) {  // the true potential on padded rows: zero rows / columns of tilde_F, zero coordinates of mu_k
-      lc.la.d = Dp;
-      for (int k = 0; k < PDEINV_MAX_PARAMS; ++k) lc.la.tp[k] = 0.f;
-      if (d->true_kind == PDEINV_POT_QUADRATIC) {
-        for (int i = 0; i < D; ++i)
-          for (int j = 0; j < D; ++j) lc.la.tp[i * Dp + j] = d->true_params[i * D + j];
-      } else {
-        PDEINV_REQUIRE(d->n_centers_true * Dp <= PDEINV_MAX_PARAMS, PDEINV_ERR_UNSUPPORTED,
-                       "kfp_mlp: padded true GMM exceeds PDEINV_MAX_PARAMS");
-        for (int k = 0; k < d->n_centers_true; ++k)
-          for (int i = 0; i < D; ++i) lc.la.tp[k * Dp + i] = d->true_params[k * D + i];
-      }
-    }
-    lc.part = wsf + fw.part;
-    lc.acc = acc;
-    lc.D = Dp;
-    for (const Set& s : sets) {
-      PDEINV_REQUIRE(s.n == 0 || s.ld >= 2 * D, PDEINV_ERR_INVALID, "kfp_mlp: row stride < 2*dim");
-      lc.la.set = s.id; lc.la.c1 = s.c1; lc.la.c2 = s.c2; lc.la.c3 = s.c3; lc.la.c0 = s.c0; lc.la.c_true = d->c_true;
-      lc.la.inv_n = s.n ? 1.f / (float)s.n : 0.f;
-      for (int64_t r0 = 0; r0 < s.n; r0 += Bc) {
-        mlpf::Chunk c{};
-        c.d = Dp; c.L = L; c.W = Wf; c.O = p.O;
-        c.R = (s.n - r0) < Bc ? (s.n - r0) : Bc;
-        c.z = s.z + r0 * s.ld;
-        c.ldz = s.ld;
-        if (Dp != D) {
-          float* rows = wsf + fw.rows;
-          const int64_t nq = c.R * 2 * Dp;
-          hipLaunchKernelGGL(mlp_pad_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, c.z, s.ld, c.R,
-                             D, Dp, rows);
-          c.z = rows;
-          c.ldz = 2 * Dp;
-        }
-        c.params = fparams; c.grad = fgrad; c.poff = poff; c.boff = boff;
-        c.c2 = s.c2; c.c3 = s.c3; c.c0 = s.c0;
-        c.ws = wsf; c.Bc = Bc;
-        // the initial / terminal sets weight V' (or V) only: no R1 / F2 (kinetic_fokker_planck.py:34-39)
-        c.first_order = s.id != 0 && s.c1 == 0.f && s.c2 == 0.f;
-        lc.zr = c.z;
-        lc.ld = c.ldz;
-        const int rc = mlpf::run_chunk(c, mlpf::LossHook{fused_loss_hook, &lc}, st);
-        if (rc) return rc;
-      }
-    }
-    if (fs.pad) {
-      hipLaunchKernelGGL(mlp_unpad_grad_kernel, dim3((unsigned)((fw.PP + 255) / 256)), dim3(256), 0, st, pm, fgrad,
-                         fw.PP, grad);
-      return check_launch("mlp_unpad_grad_kernel");
-    }
-    return PDEINV_OK;
-  }
-  Blas blas{blas_handle(dev), st, w + p.off_kpart};
-  PDEINV_REQUIRE(blas_api().ok, PDEINV_ERR_UNSUPPORTED,
-                 "kfp_mlp: impl = LIBRARY needs rocBLAS (librocblas.so.5 could not be loaded)");
-  if (!blas.h) return fail(PDEINV_ERR_HIP, "kfp_mlp: rocblas_create_handle failed");
-  if (blas_api().set_stream(blas.h, st) != rocblas_status_success) return fail(PDEINV_ERR_HIP, "kfp_mlp: rocblas_set_stream");
-  g_rocblas_calls.fetch_add(1, std::memory_order_relaxed);
-  LibRun run{p, &blas, w, params, grad, poff, boff, st, acc};
+
+  const std::unique_ptr<RowEngine> eng = kfp_engine(d);
+  int rc = eng->begin(params, grad, (float*)ws, acc, st);
+  if (rc) return rc;
+  rc = pad_true_potential(la, eng->row_dim());
+  if (rc) return rc;
   for (const Set& s : sets) {
     PDEINV_REQUIRE(s.n == 0 || s.ld >= 2 * D, PDEINV_ERR_INVALID, "kfp_mlp: row stride < 2*dim");
-    la.set = s.id; la.c1 = s.c1; la.c2 = s.c2; la.c3 = s.c3; la.c0 = s.c0; la.c_true = d->c_true;
+    la.set = s.id; la.c1 = s.c1; la.c2 = s.c2; la.c3 = s.c3; la.c0 = s.c0;
     la.inv_n = s.n ? 1.f / (float)s.n : 0.f;
-    for (int64_t r0 = 0; r0 < s.n; r0 += p.Bc) {
-      const int64_t R = (s.n - r0) < p.Bc ? (s.n - r0) : p.Bc;
-      const int rc = run.chunk(s.z + r0 * s.ld, s.ld, R, la, false);
+    // the initial / terminal sets weight V' (or V) only: no R1 / F2 (kinetic_fokker_planck.py:34-39)
+    const RowMode mode = s.id != 0 && s.c1 == 0.f && s.c2 == 0.f ? RowMode::FIRST_ORDER : RowMode::FULL;
+    for (int64_t r0 = 0; r0 < s.n; r0 += Bc) {
+      const int64_t R = (s.n - r0) < Bc ? (s.n - r0) : Bc;
+      rc = eng->chunk(s.z + r0 * s.ld, s.ld, R, la, mode, nullptr);
       if (rc) return rc;
     }
   }
-  return PDEINV_OK;
+  return eng->end();
 }
 
 // ---- KMV residual for a general (MLP) interaction Phi_theta = V_hypothesis ----------------------
@@ -867,9 +445,9 @@ extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float
 // and  mean_j Phi(y_ij)  weighted by c_it = ds2 + ds^2 + gamma ds of log rho. The loss is quadratic
 // in gbar, so its parameter adjoint is per pair once gbar is known — two passes over pair rows
 // [y_ij | v_i | u_i | w_it] (built chunk by chunk, never the whole n^2 tensor):
-//   pass 1  grad_x V of the pair rows (F1 + R1 of the library path), mean over j -> gbar (fp32 ws);
+//   pass 1  grad_x V of the pair rows (the engine's GRAD_ONLY mode), mean over j -> gbar (fp32 ws);
 //           |gbar|^2, |gbar*|^2, |gbar* - gbar|^2 with gbar* = tilde_F (x_i - xbar_t) (Phi* quadratic);
-//   pass 2  the full library path with c2 = -2 s, c0 = 2 s w_it and the input-gradient seed
+//   pass 2  the full chain with c2 = -2 s, c0 = 2 s w_it and the input-gradient seed
 //           u_i = 2 s gbar_i, s = 1 / (n^2 n_time)  (oracle/numpy_ref.py kmv_mlp_grad_analytic).
 // rows of DP >= D floats per block: the particles' D coordinates, zeros past them (the fused path's dim padding)
 template <int D, int DP = D>
@@ -995,88 +573,16 @@ __global__ void kmv_stamp_combine_kernel(const double* __restrict__ part, int64_
   acc[PDEINV_GMM_ACC_NABLA_TRUE] += n2 * inv;
 }
 
-namespace {
-struct KmvPlan {
-  MlpPlan lib;
-  int64_t ni, nj;           // pair-row block: ni particles x nj references
-  size_t off_rows, off_gbar, off_part, total;  // floats past the library plan (part: doubles)
-};
-
-KmvPlan kmv_plan(const pdeinv_kmv_mlp_desc* d) {
-  pdeinv_kfp_mlp_desc m{};
-  m.dim = d->dim; m.n_layers = d->n_layers; m.width = d->width; m.out_features = d->out_features;
-  m.chunk_rows = d->chunk_rows > 0 ? d->chunk_rows : (1 << 18);
-  KmvPlan k{};
-  k.lib = make_plan(&m);
-  const int64_t Bc = k.lib.Bc, n = d->n_rows;
-  k.nj = n <= Bc ? n : Bc;
-  k.ni = n <= Bc ? (Bc / n < n ? Bc / n : n) : 1;
-  size_t o = k.lib.total / sizeof(float);
-  auto take = [&](size_t floats) { const size_t at = o; o += (floats + 63) & ~(size_t)63; return at; };
-  k.off_rows = take((size_t)Bc * (3 * d->dim + 1));
-  k.off_gbar = take((size_t)d->n_sets * n * d->dim);
-  k.off_part = take((size_t)d->n_sets * 3 * 2);
-  k.total = o * sizeof(float);
-  return k;
-}
-}  // namespace
-
+// the gbar terms of the loss, once gbar of every particle is known (after pass 1 of either route)
 template <int D>
-static int kmv_mlp_run(const pdeinv_kmv_mlp_desc* d, const KmvPlan& k, const float* z, int64_t set_stride,
-                       int64_t ld, const float* ds, const float* params, float* w, double* acc, float* grad,
-                       hipStream_t st) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return fail(PDEINV_ERR_HIP, "kmv_mlp: hipGetDevice failed");
-  Blas blas{blas_handle(dev), st, w + k.lib.off_kpart};
-  PDEINV_REQUIRE(blas_api().ok, PDEINV_ERR_UNSUPPORTED,
-                 "kmv_mlp: impl = LIBRARY needs rocBLAS (librocblas.so.5 could not be loaded)");
-  if (!blas.h) return fail(PDEINV_ERR_HIP, "kmv_mlp: rocblas_create_handle failed");
-  if (blas_api().set_stream(blas.h, st) != rocblas_status_success) return fail(PDEINV_ERR_HIP, "kmv_mlp: rocblas_set_stream");
-  g_rocblas_calls.fetch_add(1, std::memory_order_relaxed);
-  int64_t poff[18], boff[18];
-  param_offsets(D, d->width, d->out_features, d->n_layers, poff, boff);
-  LibRun run{k.lib, &blas, w, params, grad, poff, boff, st, acc};
-  const int64_t n = d->n_rows, T = d->n_sets, rld = 3 * D + 1;
-  float* rows = w + k.off_rows;
-  float* gbar = w + k.off_gbar;
-  double* part = (double*)(w + k.off_part);
-  const double s = 1.0 / ((double)n * (double)n * (double)T);
-  if (hipMemsetAsync(gbar, 0, sizeof(float) * (size_t)T * n * D, st) != hipSuccess)
-    return fail(PDEINV_ERR_HIP, "kmv_mlp: memset");
-  MlpLossArgs la{};
-  la.d = D;
-  for (int pass = 0; pass < 2; ++pass) {
-    if (pass == 1) {
-      la.set = 3; la.uw = 1;
-      la.c1 = 0.f; la.c3 = 0.f; la.c2 = (float)(-2.0 * s); la.c0 = (float)(2.0 * s);
-    }
-    for (int64_t t = 0; t < T; ++t) {
-      for (int64_t i0 = 0; i0 < n; i0 += k.ni) {
-        const int64_t ni = (n - i0) < k.ni ? (n - i0) : k.ni;
-        for (int64_t j0 = 0; j0 < n; j0 += k.nj) {
-          const int64_t nj = (n - j0) < k.nj ? (n - j0) : k.nj;
-          const int64_t R = ni * nj;
-          hipLaunchKernelGGL(kmv_pair_rows_kernel<D>, dim3(grid_for(R)), dim3(kBlock), 0, st, z, set_stride, ld, t,
-                             i0, ni, j0, nj, n, pass ? gbar : nullptr, pass ? ds : nullptr, d->gamma,
-                             (float)(2.0 * s), rows);
-          const int rc = run.chunk(rows, rld, R, la, pass == 0);
-          if (rc) return rc;
-          if (pass == 0)
-            hipLaunchKernelGGL(kmv_group_mean_kernel<D>, dim3((unsigned)ni), dim3(kBlock), 0, st, run.G(), nj,
-                               (float)(1.0 / (double)n), gbar + (t * n + i0) * D);
-        }
-      }
-    }
-    if (pass == 0) {
-      KmvTrueArgs ta{};
-      for (int q = 0; q < D * D; ++q) ta.F[q] = d->tilde_F[q];
-      hipLaunchKernelGGL(kmv_stamp_terms_kernel<D>, dim3((unsigned)T), dim3(kBlock), 0, st, ta, z, set_stride, ld, n,
-                         gbar, part);
-      hipLaunchKernelGGL(kmv_stamp_combine_kernel, dim3(1), dim3(64), 0, st, part, T, 1.0 / ((double)n * (double)T),
-                         acc);
-    }
-  }
-  return check_launch("kmv_mlp kernels");
+static void kmv_stamp_terms(const pdeinv_kmv_mlp_desc* d, const float* z, int64_t set_stride, int64_t ld,
+                            const float* gbar, double* part, double* acc, hipStream_t st) {
+  KmvTrueArgs ta{};
+  for (int q = 0; q < D * D; ++q) ta.F[q] = d->tilde_F[q];
+  const int64_t n = d->n_rows, T = d->n_sets;
+  hipLaunchKernelGGL(kmv_stamp_terms_kernel<D>, dim3((unsigned)T), dim3(kBlock), 0, st, ta, z, set_stride, ld, n, gbar,
+                     part);
+  hipLaunchKernelGGL(kmv_stamp_combine_kernel, dim3(1), dim3(64), 0, st, part, T, 1.0 / ((double)n * (double)T), acc);
 }
 
 // the narrow-net pair kernels (mlp_pairs.hip): pairs generated in registers, MFMA weight gradients
@@ -1092,16 +598,14 @@ static bool kmv_use_pairs(const pdeinv_kmv_mlp_desc* d) {
   return d->impl != PDEINV_MLP_IMPL_LIBRARY && kmv_pairs_supported(d);
 }
 
-// ---- wide general-Phi nets (width >= 32): the pair rows through the fused fp32-MFMA path ------------
-// Pair rows [y_ij | v_i | u_i | w_it] are built chunk by chunk exactly as for the library path, then run
-// through mlpf::run_chunk (the C5 machinery: B-resident row GEMMs, LDS-free weight gradients) — pass 1 in
-// its grad-only mode (g = grad_x Phi per pair -> mean over j), pass 2 with the per-row value weight
-// w_it on c0 and the input-gradient seed u_i in the loss hook. Widths between the compiled ones are
-// zero-padded (exact, common.h MlpPadMap). No rocBLAS on this path.
+// ---- the row route: pair rows through a row engine ---------------------------------------------------
+// Wide general-Phi nets (width >= 32) run their pair rows through the fused engine (the C5 machinery: B-resident
+// row GEMMs, LDS-free weight gradients; widths between the compiled ones zero-padded, no rocBLAS); impl = LIBRARY
+// runs the same rows through the rocBLAS engine (dim <= 8).
 static pdeinv_kfp_mlp_desc kmv_as_kfp(const pdeinv_kmv_mlp_desc* d) {
   pdeinv_kfp_mlp_desc m{};
   m.dim = d->dim; m.n_layers = d->n_layers; m.width = d->width; m.out_features = d->out_features;
-  m.chunk_rows = d->chunk_rows > 0 ? d->chunk_rows : (1 << 18);
+  m.chunk_rows = d->chunk_rows;
   m.impl = d->impl;
   return m;
 }
@@ -1114,122 +618,78 @@ static bool kmv_use_fused(const pdeinv_kmv_mlp_desc* d) {
 }
 
 namespace {
-struct KmvFusedPlan {
-  int Wf, Dp;
-  bool pad;
-  int64_t Bc, ni, nj, PP;
-  MlpPadMap pm;
-  size_t fl, off_part, off_pbuf, off_gbuf, off_rows, off_gbar, off_spart, total;  // floats
+std::unique_ptr<RowEngine> kmv_rows_engine(const pdeinv_kmv_mlp_desc* d) {
+  const pdeinv_kfp_mlp_desc m = kmv_as_kfp(d);
+  FusedShape f;
+  if (kmv_use_fused(d) && fused_shape(&m, &f)) return std::make_unique<FusedEngine>(m, f, true, "kmv_mlp");
+  return make_library_engine(m, "kmv_mlp");
+}
+
+// the pair-row blocking and the driver's tail of the workspace, behind the engine's floats
+struct KmvRowsPlan {
+  int64_t ni, nj;                              // pair-row block: ni particles x nj references
+  size_t off_rows, off_gbar, off_part, total;  // floats (part: doubles); total in bytes
 };
 
-KmvFusedPlan kmv_fused_plan(const pdeinv_kmv_mlp_desc* d) {
+KmvRowsPlan kmv_rows_plan(const pdeinv_kmv_mlp_desc* d, const RowEngine& eng) {
   const pdeinv_kfp_mlp_desc m = kmv_as_kfp(d);
-  KmvFusedPlan k{};
-  FusedShape fs;
-  fused_shape(&m, &fs);
-  k.Wf = fs.Wp;
-  k.Dp = fs.Dp;
-  k.pad = fs.pad;
-  k.Bc = m.chunk_rows;
-  const int64_t n = d->n_rows;
-  k.nj = n <= k.Bc ? n : k.Bc;
-  k.ni = n <= k.Bc ? (k.Bc / n < n ? k.Bc / n : n) : 1;
-  if (k.pad) {
-    k.pm = width_pad_map(&m, fs);
-    k.PP = k.pm.padded_count();
-  }
-  size_t o = 0;
+  const int64_t Bc = chunk_rows_of(&m), n = d->n_rows;
+  KmvRowsPlan k{};
+  k.nj = n <= Bc ? n : Bc;
+  k.ni = n <= Bc ? (Bc / n < n ? Bc / n : n) : 1;
+  size_t o = eng.ws_floats();
   auto take = [&](size_t floats) { const size_t at = o; o += (floats + 63) & ~(size_t)63; return at; };
-  k.fl = take(mlpf::workspace_floats(k.Dp, d->n_layers, k.Wf, d->out_features, k.Bc));
-  k.off_part = take((size_t)PDEINV_GMM_NACC * kLossGrid);
-  k.off_pbuf = take((size_t)k.PP);
-  k.off_gbuf = take((size_t)k.PP);
-  k.off_rows = take((size_t)k.Bc * (3 * k.Dp + 1));
+  k.off_rows = take((size_t)Bc * (3 * eng.row_dim() + 1));
   k.off_gbar = take((size_t)d->n_sets * n * d->dim);
-  k.off_spart = take((size_t)d->n_sets * 3 * 2);
+  k.off_part = take((size_t)d->n_sets * 3 * 2);
   k.total = o * sizeof(float);
   return k;
 }
 }  // namespace
 
-// D = the particles' dim, DP = the fused kernels' (D zero-padded to 2 / 4 / 8: the pair rows carry the padding)
+// D = the particles' dim, DP = the engine's row_dim() (fused: D zero-padded to 2 / 4 / 8 / 16, the pair rows
+// carry the padding)
 template <int D, int DP>
-static int kmv_fused_run(const pdeinv_kmv_mlp_desc* d, const KmvFusedPlan& k, const float* z, int64_t set_stride,
-                         int64_t ld, const float* ds, const float* params, float* w, double* acc, float* grad,
-                         hipStream_t st) {
-  const int L = d->n_layers, O = d->out_features;
-  int64_t poff[18], boff[18];
-  param_offsets(DP, k.Wf, O, L, poff, boff);
-  const float* fparams = params;
-  float* fgrad = grad;
-  if (k.pad) {
-    float* pbuf = w + k.off_pbuf;
-    fgrad = w + k.off_gbuf;
-    hipLaunchKernelGGL(mlp_pad_params_kernel, dim3((unsigned)((k.PP + 255) / 256)), dim3(256), 0, st, k.pm, params,
-                       k.PP, pbuf);
-    if (hipMemsetAsync(fgrad, 0, sizeof(float) * k.PP, st) != hipSuccess) return fail(PDEINV_ERR_HIP, "kmv_mlp: memset");
-    fparams = pbuf;
-  }
+static int kmv_rows_run(const pdeinv_kmv_mlp_desc* d, RowEngine& eng, const float* z, int64_t set_stride, int64_t ld,
+                        const float* ds, const float* params, float* w, double* acc, float* grad, hipStream_t st) {
+  const KmvRowsPlan k = kmv_rows_plan(d, eng);
+  int rc = eng.begin(params, grad, w, acc, st);
+  if (rc) return rc;
   const int64_t n = d->n_rows, T = d->n_sets, rld = 3 * DP + 1;
   float* rows = w + k.off_rows;
   float* gbar = w + k.off_gbar;
-  double* part = (double*)(w + k.off_spart);
+  double* part = (double*)(w + k.off_part);
   const double s = 1.0 / ((double)n * (double)n * (double)T);
   if (hipMemsetAsync(gbar, 0, sizeof(float) * (size_t)T * n * D, st) != hipSuccess)
     return fail(PDEINV_ERR_HIP, "kmv_mlp: memset");
-  LossCtx lc{};
-  lc.la.d = DP;
-  lc.la.set = 3;
-  lc.la.uw = 1;
-  lc.la.c2 = (float)(-2.0 * s);
-  lc.la.c0 = (float)(2.0 * s);
-  lc.part = w + k.off_part;
-  lc.acc = acc;
-  lc.D = DP;
-  lc.zr = rows;
-  lc.ld = rld;
-  mlpf::Chunk c{};
-  c.d = DP; c.L = L; c.W = k.Wf; c.O = O;
-  c.z = rows; c.ldz = rld;
-  c.params = fparams; c.grad = fgrad; c.poff = poff; c.boff = boff;
-  c.ws = w; c.Bc = k.Bc;
+  MlpLossArgs la{};
+  la.d = DP;
   for (int pass = 0; pass < 2; ++pass) {
-    c.grad_only = pass == 0;
-    c.c2 = pass ? lc.la.c2 : 0.f;
-    c.c3 = 0.f;
-    c.c0 = pass ? lc.la.c0 : 0.f;
-    c.wrow = pass ? rows + 3 * DP : nullptr;
-    c.ldw = rld;
+    if (pass == 1) {
+      la.set = 3; la.uw = 1;
+      la.c1 = 0.f; la.c3 = 0.f; la.c2 = (float)(-2.0 * s); la.c0 = (float)(2.0 * s);
+    }
     for (int64_t t = 0; t < T; ++t) {
       for (int64_t i0 = 0; i0 < n; i0 += k.ni) {
         const int64_t ni = (n - i0) < k.ni ? (n - i0) : k.ni;
         for (int64_t j0 = 0; j0 < n; j0 += k.nj) {
           const int64_t nj = (n - j0) < k.nj ? (n - j0) : k.nj;
-          c.R = ni * nj;
-          hipLaunchKernelGGL((kmv_pair_rows_kernel<D, DP>), dim3(grid_for(c.R)), dim3(kBlock), 0, st, z, set_stride, ld,
+          const int64_t R = ni * nj;
+          hipLaunchKernelGGL((kmv_pair_rows_kernel<D, DP>), dim3(grid_for(R)), dim3(kBlock), 0, st, z, set_stride, ld,
                              t, i0, ni, j0, nj, n, pass ? gbar : nullptr, pass ? ds : nullptr, d->gamma,
                              (float)(2.0 * s), rows);
-          const int rc = mlpf::run_chunk(c, mlpf::LossHook{fused_loss_hook, &lc}, st);
+          rc = eng.chunk(rows, rld, R, la, pass ? RowMode::FULL : RowMode::GRAD_ONLY, pass ? rows + 3 * DP : nullptr);
           if (rc) return rc;
           if (pass == 0)
             hipLaunchKernelGGL((kmv_group_mean_kernel<D, DP>), dim3((unsigned)ni), dim3(kBlock), 0, st,
-                               mlpf::grad_rows(c), nj, (float)(1.0 / (double)n), gbar + (t * n + i0) * D);
+                               eng.grad_rows(), nj, (float)(1.0 / (double)n), gbar + (t * n + i0) * D);
         }
       }
     }
-    if (pass == 0) {
-      KmvTrueArgs ta{};
-      for (int q = 0; q < D * D; ++q) ta.F[q] = d->tilde_F[q];
-      hipLaunchKernelGGL(kmv_stamp_terms_kernel<D>, dim3((unsigned)T), dim3(kBlock), 0, st, ta, z, set_stride, ld, n,
-                         gbar, part);
-      hipLaunchKernelGGL(kmv_stamp_combine_kernel, dim3(1), dim3(64), 0, st, part, T, 1.0 / ((double)n * (double)T),
-                         acc);
-    }
+    if (pass == 0) kmv_stamp_terms<D>(d, z, set_stride, ld, gbar, part, acc, st);
   }
-  if (k.pad)
-    hipLaunchKernelGGL(mlp_unpad_grad_kernel, dim3((unsigned)((k.PP + 255) / 256)), dim3(256), 0, st, k.pm, fgrad,
-                       k.PP, grad);
-  return check_launch("kmv_mlp fused kernels");
+  rc = eng.end();
+  return rc ? rc : check_launch("kmv_mlp kernels");
 }
 
 static size_t kmv_pairs_part_offset(const pdeinv_kmv_mlp_desc* d) { return (kmv_pairs_workspace_bytes(d) + 255) & ~(size_t)255; }
@@ -1247,8 +707,7 @@ extern "C" size_t pdeinv_residual_kmv_mlp_workspace_bytes(const pdeinv_kmv_mlp_d
   if (!d || d->dim < 1 || d->n_layers < 1 || d->width < 1 || d->out_features < 1 || d->n_sets < 1 || d->n_rows < 1)
     return 0;
   if (kmv_use_pairs(d)) return kmv_pairs_part_offset(d) + sizeof(double) * (size_t)d->n_sets * 3;
-  if (kmv_use_fused(d)) return kmv_fused_plan(d).total;
-  return kmv_plan(d).total;
+  return kmv_rows_plan(d, *kmv_rows_engine(d)).total;
 }
 
 template <int D>
@@ -1259,12 +718,7 @@ static int kmv_pairs_orchestrate(const pdeinv_kmv_mlp_desc* d, const float* z, i
   int rc = kmv_pairs_run(d, z, set_stride, ld, ds, params, ws, acc, grad, &gbar, 0, st);
   if (rc) return rc;
   double* part = (double*)((char*)ws + kmv_pairs_part_offset(d));
-  KmvTrueArgs ta{};
-  for (int q = 0; q < D * D; ++q) ta.F[q] = d->tilde_F[q];
-  const int64_t n = d->n_rows, T = d->n_sets;
-  hipLaunchKernelGGL(kmv_stamp_terms_kernel<D>, dim3((unsigned)T), dim3(kBlock), 0, st, ta, z, set_stride, ld, n, gbar,
-                     part);
-  hipLaunchKernelGGL(kmv_stamp_combine_kernel, dim3(1), dim3(64), 0, st, part, T, 1.0 / ((double)n * (double)T), acc);
+  kmv_stamp_terms<D>(d, z, set_stride, ld, gbar, part, acc, st);
   rc = check_launch("kmv_stamp kernels");
   if (rc) return rc;
   return kmv_pairs_run(d, z, set_stride, ld, ds, params, ws, acc, grad, nullptr, 1, st);
@@ -1295,20 +749,14 @@ extern "C" int pdeinv_residual_kmv_mlp(const pdeinv_kmv_mlp_desc* d, const float
 #undef CASE
     }
   }
-  if (kmv_use_fused(d)) {
-    const KmvFusedPlan k = kmv_fused_plan(d);
-    switch (d->dim) {
+  // the library engine computes in the particles' dim (1..8), the fused engine in the next compiled one
+  const std::unique_ptr<RowEngine> eng = kmv_rows_engine(d);
+  switch (d->dim * 32 + eng->row_dim()) {
 #define CASE(DD, DDP) \
-  case DD: return kmv_fused_run<DD, DDP>(d, k, z, set_stride, ld, ds, params, (float*)ws, acc, grad, st);
-      CASE(1, 2) CASE(2, 2) CASE(3, 4) CASE(4, 4) CASE(5, 8) CASE(6, 8) CASE(7, 8) CASE(8, 8)
-      CASE(9, 16) CASE(10, 16) CASE(11, 16) CASE(12, 16) CASE(13, 16) CASE(14, 16) CASE(15, 16) CASE(16, 16)
-#undef CASE
-    }
-  }
-  const KmvPlan k = kmv_plan(d);
-  switch (d->dim) {
-#define CASE(DD) case DD: return kmv_mlp_run<DD>(d, k, z, set_stride, ld, ds, params, (float*)ws, acc, grad, st);
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+  case DD * 32 + DDP: return kmv_rows_run<DD, DDP>(d, *eng, z, set_stride, ld, ds, params, (float*)ws, acc, grad, st);
+    CASE(1, 1) CASE(2, 2) CASE(3, 3) CASE(4, 4) CASE(5, 5) CASE(6, 6) CASE(7, 7) CASE(8, 8)
+    CASE(1, 2) CASE(3, 4) CASE(5, 8) CASE(6, 8) CASE(7, 8)
+    CASE(9, 16) CASE(10, 16) CASE(11, 16) CASE(12, 16) CASE(13, 16) CASE(14, 16) CASE(15, 16) CASE(16, 16)
 #undef CASE
     default:
       return fail(PDEINV_ERR_UNSUPPORTED, "kmv_mlp: dim must be in [1, 8]");

@@ -5,14 +5,15 @@
 namespace pdeinv {
 namespace mlpf {
 
-// Shapes the fused path handles (else the rocBLAS path runs).
+// Shapes the kernels are compiled for. mlp.hip fused_shape zero-pads every other dim <= 16 and width <= 1024 to
+// one of them; a shape outside that envelope is UNSUPPORTED (rocBLAS runs only under the opt-in impl = LIBRARY).
 bool supported(int d, int L, int W, int O);
 
 // Workspace (floats) for chunks of Bc rows.
 size_t workspace_floats(int d, int L, int W, int O, int64_t Bc);
 
 // Per-set loss hook: the orchestrator computes g [R x d] and the per-row terms (V', V''), then
-// calls this to accumulate the loss slots and write abar0 = 2 c1 g [R x d] (mlp.hip's loss kernel).
+// calls this to accumulate the loss slots and write abar0 = 2 c1 g [R x d] (mlp.hip launch_mlp_loss).
 // terms[r] = {V', V'', V, 0}.
 struct LossHook {
   int (*fn)(void* ctx, const float* g, const float4* terms, float* abar0, int64_t R, hipStream_t st);

@@ -1,6 +1,6 @@
 // mlp_fused.hip — the V_hypothesis KFP residual on hand-written fp32 MFMA kernels (gfx950).
 //
-// Same algebra as mlp.hip's library path (oracle/numpy_ref.py kfp_mlp_grad_analytic), but the
+// Same algebra as the rocBLAS engine of mlp_library.hip (oracle/numpy_ref.py kfp_mlp_grad_analytic), but the
 // element-wise steps ride in GEMM prologues (building the A operand in LDS) or epilogues (on the
 // accumulators). The first hidden layer has K = d (<= 16) inputs, so its streams come from small
 // VALU kernels over the sample rows (h1 planes, abar1, g, and the layer-1 parameter gradient).
@@ -23,7 +23,7 @@
 //   R1    a2 = (2y) Ko^T                                                E: store
 //   R1    a1 = (s1(h2) a2) K2^T                                         E: store
 //   g     g = (s1(z1) a1) K1^T                 VALU, one wave per row (layer-1 recompute)
-//   loss  (mlp.hip)  per-row terms, abar0 = 2 c1 g
+//   loss  (mlp.hip launch_mlp_loss)  per-row terms, abar0 = 2 c1 g
 //   F2    zetabar2 = abar1 K2                  A: abar1 = s1(z1) (abar0 K1) from the rows   E: store
 //   UB    ubar = (s1(h2) zetabar2) Ko                                   E: seeds ybar.., bo grad
 //   R2    hbar2 streams = ybar streams Ko^T                             E: act_bwd -> zbar2, b2 grad

@@ -2,7 +2,7 @@
 // registers (gfx950).
 //
 // Replaces, for width <= 28 (the reference's default V_hypothesis is width 20 x 8 layers,
-// configurations/neural_network/MLP.yaml:4-5), the pair-row + rocBLAS path of mlp.hip for
+// configurations/neural_network/MLP.yaml:4-5), the pair-row route of mlp.hip (kmv_rows_run) for
 // methods/consistency_instances/kinetic_mckean_vlasov.py:11-120 with a non-parametric Phi_theta:
 // every pair (i, j) of a time stamp's particles, y_ij = x_i - x_j (x_minus_ref, :20-23), needs
 // grad Phi(y_ij), v_i^T Hess Phi(y_ij) v_i and Phi(y_ij), and the loss' parameter gradient.

@@ -321,6 +321,36 @@ def test_abi_argument_validation_without_gpu():
     assert call() == native.PDEINV_ERR_UNSUPPORTED and b"LIBRARY" in L.pdeinv_last_error()
 
 
+def test_mlp_workspace_bytes_are_pinned():
+    """The two MLP workspace queries (pure host code) return the byte counts recorded from the build before the
+    row-engine refactor of csrc/mlp.hip: engine region, then the driver's own tail, on every route."""
+    from utils import native
+    L = native.lib()
+    A, LIB, FU, PR = native.MLP_IMPL_AUTO, native.MLP_IMPL_LIBRARY, native.MLP_IMPL_FUSED, native.MLP_IMPL_PAIRS_RING
+    kfp = {  # (dim, layers, width, out, chunk_rows, impl)
+        (2, 2, 256, 40, 0, A): 3552592128,
+        (3, 2, 100, 40, 4096, A): 47446784,
+        (4, 3, 64, 80, 0, FU): 1867858176,
+        (2, 2, 20, 40, 4096, LIB): 16793600,
+        (10, 1, 32, 1, 0, LIB): 602947584,
+    }
+    for t, want in kfp.items():
+        d = native.KfpMlpDesc()
+        d.dim, d.n_layers, d.width, d.out_features, d.chunk_rows, d.impl = t
+        assert L.pdeinv_residual_kfp_mlp_workspace_bytes(ctypes.byref(d)) == want, t
+    kmv = {  # (dim, layers, width, out, n_sets, n_rows, chunk_rows, impl)
+        (2, 8, 20, 40, 3, 130, 0, A): 14196808,
+        (2, 8, 24, 40, 1, 100, 0, PR): 26710552,
+        (3, 2, 64, 40, 3, 45, 300, FU): 5772032,
+        (12, 2, 64, 40, 3, 40, 300, A): 6132736,
+        (2, 2, 64, 40, 3, 60, 300, LIB): 7079936,
+    }
+    for t, want in kmv.items():
+        d = native.KmvMlpDesc()
+        d.dim, d.n_layers, d.width, d.out_features, d.n_sets, d.n_rows, d.chunk_rows, d.impl = t
+        assert L.pdeinv_residual_kmv_mlp_workspace_bytes(ctypes.byref(d)) == want, t
+
+
 def test_bench_refuses_mismatched_world_size():
     """bench.py exits non-zero, printing no line, when torch.distributed.run's WORLD_SIZE disagrees with
     --gpus (checked before any GPU call, so it runs here), and rejects --gpus 0."""
