@@ -33,6 +33,12 @@
 //         from the rows in the A prologue: the h1 / abar1 planes never exist)
 // First-order chunks (the initial / terminal sets, c1 = c2 = 0; W in {128, 256}) run run_chunk_fo2 instead: the
 // same steps on two streams [h, z'] / [zbar, z'bar], without R1, g, F2 and UB (see there).
+//
+// Where the formulas live: the forward streams of a layer are fwd_streams (from its planes) and l1_streams (layer 1,
+// from the row projections), next to ftanh; a_operand holds the switch over the plane A-operand modes (store_a,
+// rgemm, rgemm16); fwgrad and wgrad2 call the two stream helpers directly. The epilogues E_ACT_FWD, E_STORE /
+// E_STORE3 and E_OUT are epi_act_fwd, epi_store and epi_out, the E_OUT row reduction is out_row_terms (above fgemm);
+// E_SEEDS, E_OUT_SEEDS1, E_ACT_BWD and the bias-gradient tail are written in each kernel.
 #include <math.h>
 
 #include <algorithm>
@@ -63,22 +69,49 @@ __device__ __forceinline__ float ftanh(float z) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
+// ---- the stream formulas of kfp_mlp_grad_analytic (with h = tanh(z): s1 = 1 - h^2, s2 = -2 h s1). The callers
+//      mask rows / columns out of range themselves. ----
+// Forward streams of a tanh layer from its stored planes p = [h, z', z'', zetabar]:
+//   v = [h, s1 z', s1 z'' + s2 z'^2, s1 zetabar], the first NS of both
+template <int NS>
+__device__ __forceinline__ void fwd_streams(const float (&p)[NS], float (&v)[NS]) {
+  static_assert(NS >= 2 && NS <= 4, "fwd_streams: 2, 3 or 4 streams");
+  const float h = p[0], zd = p[1];
+  [[maybe_unused]] const float s1 = 1.f - h * h, s2 = -2.f * h * s1;  // s2: unused (and gone) at NS = 2
+  v[0] = h;
+  v[1] = s1 * zd;
+  if constexpr (NS > 2) v[2] = fmaf(s1, p[2], s2 * zd * zd);
+  if constexpr (NS > 3) v[3] = s1 * p[3];
+}
+// The same streams of layer 1 from its projections z = x K1 + b1, zy = v K1 (so z1'' = 0) and, fourth stream,
+// zb = abar0 K1:  v = [h1, s1 zy, -2 h1 s1 zy^2, s1 zb]
+template <int NS>
+__device__ __forceinline__ void l1_streams(float (&v)[NS], float z, float zy, float zb = 0.f) {
+  static_assert(NS >= 2 && NS <= 4, "l1_streams: 2, 3 or 4 streams");
+  const float h = ftanh(z), s1 = 1.f - h * h;
+  v[0] = h;
+  v[1] = s1 * zy;
+  if constexpr (NS > 2) v[2] = -2.f * h * s1 * zy * zy;
+  if constexpr (NS > 3) v[3] = s1 * zb;
+}
+
 // 32-bit byte offsets from a uniform base (saddr addressing): a chunk's planes stay at or below 2^30 floats
 // (byte offsets < 2^32, unsigned; run_chunk checks Bc * max(W, out) <= 2^30)
 // Plane accesses keep the default cache policy (non-temporal plane loads everywhere measured C5 +10 ms: the planes
 // re-read by later products lose their cache hits; non-temporal epilogue stores everywhere were mixed,
-// profiles/r05_c5_out16_nt_ab.txt), except two streams that are touched once:
+// profiles/r05_c5_out16_nt_ab.txt), except two streams that are touched once: stores with CP_STREAM, named where the
+// epilogue is called (rgemm), and the R2a epilogue below.
+enum { CP_DEFAULT = 0, CP_STREAM };
 __device__ __forceinline__ float ldo(const float* base, uint32_t idx) {
   return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (idx << 2));
 }
+template <int CP = CP_DEFAULT>
 __device__ __forceinline__ void sto(float* base, uint32_t idx, float v) {
-  *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (idx << 2)) = v;
+  float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (idx << 2));
+  if constexpr (CP == CP_STREAM) __builtin_nontemporal_store(v, p);
+  else *p = v;
 }
-// the hbar1 planes (written by R2b, read once by l1_grad_kernel): l1_grad 3.79 -> 3.60 ms, R2b 13.61 -> 13.49 ms
-// (profiles/r05_c5_nt_hb1_ab.txt)
-__device__ __forceinline__ void sto_h(float* base, uint32_t idx, float v) {
-  __builtin_nontemporal_store(v, reinterpret_cast<float*>(reinterpret_cast<char*>(base) + (idx << 2)));
-}
+// l1_grad_kernel's read of the hbar1 planes (the other end of rgemm's CP_STREAM stores)
 __device__ __forceinline__ float ld_h(const float* p) { return __builtin_nontemporal_load(p); }
 // the streaming epilogue of the K = out_features reverse product (R2a: five planes in, three out, 1.3 B of plane
 // traffic per FLOP): C5 R2a 8.01 -> 7.79 ms, the products that re-read its planes unchanged
@@ -136,6 +169,30 @@ struct GemmArgs {
 
 template <int AM>
 constexpr bool a_is_l1() { return AM == A_L1F || AM == A_L1A; }
+// source planes the A operand of a plane mode reads per element (the layer-1 modes read none)
+template <int AM>
+constexpr int a_planes() {
+  return (AM == A_FWD || AM == A_S3) ? 3
+         : ((AM == A_S1MUL || AM == A_FWD2 || AM == A_S2) ? 2 : ((AM == A_U || AM == A_RAW1) ? 1 : 0));
+}
+// The A operand's S streams av of one element from its source planes p (plane modes; store_a, rgemm)
+template <int AM, int S>
+__device__ __forceinline__ void a_operand(const float (&p)[a_planes<AM>()], float (&av)[S]) {
+  static_assert(!a_is_l1<AM>(), "a_operand: plane modes (the layer-1 modes build theirs with l1_streams)");
+  if constexpr (AM == A_FWD || AM == A_FWD2) {
+    fwd_streams<S>(p, av);
+  } else if constexpr (AM == A_S1MUL) {
+    const float h = p[0];
+    av[0] = (1.f - h * h) * p[1];
+  } else if constexpr (AM == A_U) {
+    av[0] = 2.f * p[0];
+  } else {  // A_RAW1, A_S2, A_S3: the planes as they are
+    av[0] = p[0];
+    if constexpr (S > 1) av[1] = p[1];
+    if constexpr (S > 2) av[2] = p[2];
+  }
+}
+
 template <int D>
 constexpr int k1_stride() { return (D + 1 + 3) & ~3; }  // K1^T row: d weights, b1, pad to 16 B
 
@@ -162,8 +219,9 @@ __device__ __forceinline__ void l1_project(const float* x, const float* y, const
 template <int BM, int AM>
 struct ARegs {
   static constexpr int NE = BM * BK / kT;  // elements per thread
-  static constexpr int NV = (AM == A_FWD || AM == A_S3) ? 3 : ((AM == A_S1MUL || AM == A_FWD2 || AM == A_S2) ? 2 : 1);
-  float v[NE][NV > 0 ? NV : 1];
+  static constexpr int NV = a_planes<AM>();
+  static_assert(NV >= 1, "ARegs: plane modes");
+  float v[NE][NV];
 };
 
 // Loads are unconditional from a clamped 32-bit offset (a chunk's planes stay at or below 2^30 floats):
@@ -193,35 +251,11 @@ __device__ __forceinline__ void store_a(const GemmArgs& a, const ARegs<BM, AM>& 
     const int e = threadIdx.x + j * kT;
     const int m = e / BK, kk = e - m * BK;
     const bool ok = full || (r0 + m < a.R && k0 + kk < a.K);
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-    if constexpr (AM == A_FWD) {
-      const float h = ra.v[j][0], zd = ra.v[j][1], zdd = ra.v[j][2];
-      const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-      v0 = h;
-      v1 = s1 * zd;
-      v2 = fmaf(s1, zdd, s2 * zd * zd);
-    } else if constexpr (AM == A_S1MUL) {
-      const float h = ra.v[j][0];
-      v0 = (1.f - h * h) * ra.v[j][1];
-    } else if constexpr (AM == A_U) {
-      v0 = 2.f * ra.v[j][0];
-    } else if constexpr (AM == A_RAW1) {
-      v0 = ra.v[j][0];
-    } else if constexpr (AM == A_FWD2) {
-      const float h = ra.v[j][0];
-      v0 = h;
-      v1 = (1.f - h * h) * ra.v[j][1];
-    } else if constexpr (AM == A_S2) {
-      v0 = ra.v[j][0];
-      v1 = ra.v[j][1];
-    } else {  // A_S3
-      v0 = ra.v[j][0];
-      v1 = ra.v[j][1];
-      v2 = ra.v[j][2];
-    }
-    As[kk * LDA + m] = ok ? v0 : 0.f;
-    if constexpr (S > 1) As[(BK + kk) * LDA + m] = ok ? v1 : 0.f;
-    if constexpr (S > 2) As[(2 * BK + kk) * LDA + m] = ok ? v2 : 0.f;
+    float av[S];
+    a_operand<AM, S>(ra.v[j], av);
+    As[kk * LDA + m] = ok ? av[0] : 0.f;
+    if constexpr (S > 1) As[(BK + kk) * LDA + m] = ok ? av[1] : 0.f;
+    if constexpr (S > 2) As[(2 * BK + kk) * LDA + m] = ok ? av[2] : 0.f;
   }
 }
 
@@ -260,6 +294,45 @@ __device__ __forceinline__ void store_b(const GemmArgs& a, const float (&rb)[BK 
     const bool ok = full || (k0 + kk < a.K && n0 + nn < a.N);
     Bs[kk * LDB + nn] = ok ? rb[j] : 0.f;
   }
+}
+
+// ---- row-GEMM epilogues on one element of C (c0..c2 = its streams, o = r N + n, bn = bias[n]); the kernels keep
+//      their loops, fragment maps and bounds checks. The modes not here stay per kernel. ----
+template <int S>
+__device__ __forceinline__ void epi_act_fwd(const GemmArgs& a, uint32_t o, float c0, float c1, float c2, float bn) {
+  sto(a.po0, o, ftanh(c0 + bn));
+  sto(a.po1, o, c1);
+  if constexpr (S > 2) sto(a.po2, o, c2);
+}
+template <int S, int CP>  // E_STORE (S = 1), E_STORE3 (S = 2, 3)
+__device__ __forceinline__ void epi_store(const GemmArgs& a, uint32_t o, float c0, float c1, float c2) {
+  sto<CP>(a.po0, o, c0);
+  if constexpr (S > 1) sto<CP>(a.po1, o, c1);
+  if constexpr (S > 2) sto<CP>(a.po2, o, c2);
+}
+// E_OUT: the y streams out, and the row's sums t = [y^2, y y', y'^2 + y y''] (out_row_terms finishes them)
+__device__ __forceinline__ void epi_out(const GemmArgs& a, uint32_t o, float c0, float yd, float ydd, float bn,
+                                        float& t0, float& t1, float& t2) {
+  const float y = c0 + bn;
+  sto(a.po0, o, y);
+  sto(a.po1, o, yd);
+  sto(a.po2, o, ydd);
+  t0 = fmaf(y, y, t0);
+  t1 = fmaf(y, yd, t1);
+  t2 = fmaf(yd, yd, fmaf(y, ydd, t2));
+}
+// E_OUT / E_OUT_SEEDS1 after the column loop: sum the row's partial sums over the LW lanes that hold its columns
+// (32: 32x32 fragments, 16: 16x16) and write the row's {V', V'', V, 0} into column block cb's terms
+// (out_features > one block: one partial per column block, summed by terms_sum_kernel)
+template <int LW>
+__device__ __forceinline__ void out_row_terms(const GemmArgs& a, int cb, int r, float p0, float p1, float p2) {
+#pragma unroll
+  for (int off = LW / 2; off > 0; off >>= 1) {
+    p0 += __shfl_xor(p0, off, 64);
+    p1 += __shfl_xor(p1, off, 64);
+    p2 += __shfl_xor(p2, off, 64);
+  }
+  if ((threadIdx.x & (LW - 1)) == 0 && r < a.R) a.terms[(int64_t)cb * a.R + r] = make_float4(2.f * p1, 2.f * p2, p0, 0.f);
 }
 
 template <int S, int BM, int BN, int WGM, int AM, int BMD, int EM, int D = 0>
@@ -324,6 +397,7 @@ __global__ __launch_bounds__(kT, 2) void fgemm(GemmArgs a) {
           const float* kc = k1s + (ok ? k0 + kk : 0) * k1_stride<D>();
           float z, zy;
           l1_project<D>(rx, ry, kc, z, zy);
+          // l1_streams, written out: the helper changes these kernels' code
           const float h = ftanh(z), s1 = 1.f - h * h;
           if constexpr (AM == A_L1F) {
             As[kk * LDA + m] = ok ? h : 0.f;
@@ -388,30 +462,14 @@ __global__ __launch_bounds__(kT, 2) void fgemm(GemmArgs a) {
             const int r = r0 + wm * WM + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * hi;
             const bool ok = !CHECK || (nv && r < a.R);
             const uint32_t o = (uint32_t)(r * a.N + n);
+            [[maybe_unused]] constexpr int s1i = S > 1 ? 1 : 0;  // the streams an S < 3 mode lacks repeat stream 0
             if constexpr (EM == E_ACT_FWD) {
-              if (ok) {
-                sto(a.po0, o, ftanh(acc[0][mi][ni][q] + bn));
-                sto(a.po1, o, acc[1][mi][ni][q]);
-                if constexpr (S > 2) sto(a.po2, o, acc[S - 1][mi][ni][q]);
-              }
-            } else if constexpr (EM == E_STORE) {
-              if (ok) sto(a.po0, o, acc[0][mi][ni][q]);
-            } else if constexpr (EM == E_STORE3) {
-              if (ok) {
-                sto(a.po0, o, acc[0][mi][ni][q]);
-                sto(a.po1, o, acc[1][mi][ni][q]);
-                if constexpr (S > 2) sto(a.po2, o, acc[S - 1][mi][ni][q]);
-              }
+              if (ok) epi_act_fwd<S>(a, o, acc[0][mi][ni][q], acc[s1i][mi][ni][q], acc[S - 1][mi][ni][q], bn);
+            } else if constexpr (EM == E_STORE || EM == E_STORE3) {
+              if (ok) epi_store<S, CP_DEFAULT>(a, o, acc[0][mi][ni][q], acc[s1i][mi][ni][q], acc[S - 1][mi][ni][q]);
             } else if constexpr (EM == E_OUT) {
-              if (ok) {
-                const float y = acc[0][mi][ni][q] + bn, yd = acc[1][mi][ni][q], ydd = acc[2][mi][ni][q];
-                sto(a.po0, o, y);
-                sto(a.po1, o, yd);
-                sto(a.po2, o, ydd);
-                t0[q] = fmaf(y, y, t0[q]);
-                t1[q] = fmaf(y, yd, t1[q]);
-                t2[q] = fmaf(yd, yd, fmaf(y, ydd, t2[q]));
-              }
+              if (ok)
+                epi_out(a, o, acc[0][mi][ni][q], acc[1][mi][ni][q], acc[2][mi][ni][q], bn, t0[q], t1[q], t2[q]);
             } else if constexpr (EM == E_SEEDS) {
               if (ok) {
                 const float ub = acc[0][mi][ni][q];
@@ -450,16 +508,8 @@ __global__ __launch_bounds__(kT, 2) void fgemm(GemmArgs a) {
         if constexpr (EM == E_OUT) {
   #pragma unroll
           for (int q = 0; q < 16; ++q) {
-            float p0 = t0[q], p1 = t1[q], p2 = t2[q];
-  #pragma unroll
-            for (int off = 16; off > 0; off >>= 1) {
-              p0 += __shfl_xor(p0, off, 64);
-              p1 += __shfl_xor(p1, off, 64);
-              p2 += __shfl_xor(p2, off, 64);
-            }
             const int r = r0 + wm * WM + mi * 32 + (q & 3) + 8 * (q >> 2) + 4 * hi;
-            // out_features > BN: one partial per column block (by), summed by terms_sum_kernel
-            if (l31 == 0 && r < a.R) a.terms[(int64_t)by * a.R + r] = make_float4(2.f * p1, 2.f * p2, p0, 0.f);
+            out_row_terms<32>(a, by, r, t0[q], t1[q], t2[q]);
           }
         }
       }
@@ -599,6 +649,8 @@ __global__ __launch_bounds__(kT) void l1_g_mfma_kernel(const float* __restrict__
 // (the third input stream h0'' = 0 carries nothing). Thread owns columns, loops rows; per-block
 // partial slab [(D + 1) x W] (K1 rows then b1 = the flat parameter order). FO (first-order chunks): h''bar = 0
 // and a1 = abar0 = 0, so zbar1 = s1 hb + s2 z1' h'b, z'bar1 = s1 h'b — hb2, a1 and abar0 are not read.
+// This is E_ACT_BWD (fgemm, rgemm) for layer 1 with z1'' = 0 folded in by hand; it is not shared with them: the shared
+// form would carry a literal `* 0.f` that fp32 code may not fold.
 constexpr int kL1Rows = 64;  // rows staged in LDS per step
 
 template <int D, int W, bool FO = false>
@@ -694,10 +746,10 @@ __global__ __launch_bounds__(kT) void l1_grad_kernel(const float* __restrict__ h
 }
 
 // ---- weight gradients -------------------------------------------------------------------
-// A streams: 4 stored planes | h, s1 z', s1 z'' + s2 z'^2, s1 zetabar | the layer-1 streams
-// [h1, s1 z1', s2 z1'^2, s1 (abar0 K1)] rebuilt from the sample rows (thread owns one feature, its
-// K1 column in registers; the 16 rows of a step staged in LDS one step ahead)
-enum { GA_RAW4 = 0, GA_PL, GA_L1 };
+// A streams: fwd_streams of the layer's 4 planes | l1_streams rebuilt from the sample rows (thread owns one
+// feature, its K1 column in registers; the 16 rows of a step staged in LDS one step ahead). The values are part of
+// the kernels' symbol names and stay as they were.
+enum { GA_PL = 1, GA_L1 = 2 };
 enum { GB_PL = 0, GB_SM };    // B streams: zbar0..2, s1(h) a | ybar0..2, 2 y
 
 struct WgradArgs {
@@ -806,29 +858,16 @@ __global__ __launch_bounds__(kT) void fwgrad(WgradArgs a) {
     for (int j = 0; j < NEA; ++j) {
       const int e = tid + j * kT, rr = e / BM, ii = e - rr * BM;
       const bool ok = (rows_full || rb0 + rr < rs1) && i0 + ii < a.n_in;
-      float v0, v1, v2, v3;
+      float av[4];
       if constexpr (GA == GA_L1) {
         const float* xrow = xs + (buf * BKG + rr) * XS;
         const float z = kc[D] + dotd<D>(xrow, kc), zd = dotd<D>(xrow + D, kc), zb = dotd<D>(xrow + 2 * D, kc);
-        const float h = ftanh(z), s1 = 1.f - h * h;
-        v0 = h;
-        v1 = s1 * zd;
-        v2 = -2.f * h * s1 * zd * zd;
-        v3 = s1 * zb;
+        l1_streams(av, z, zd, zb);
       } else {
-        v0 = ra[j][0]; v1 = ra[j][1]; v2 = ra[j][2]; v3 = ra[j][3];
+        fwd_streams(ra[j], av);
       }
-      if constexpr (GA == GA_PL) {
-        const float h = v0, zd = v1, zdd = v2, zeb = v3;
-        const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-        v1 = s1 * zd;
-        v2 = fmaf(s1, zdd, s2 * zd * zd);
-        v3 = s1 * zeb;
-      }
-      As[(0 * BKG + rr) * LDA + ii] = ok ? v0 : 0.f;
-      As[(1 * BKG + rr) * LDA + ii] = ok ? v1 : 0.f;
-      As[(2 * BKG + rr) * LDA + ii] = ok ? v2 : 0.f;
-      As[(3 * BKG + rr) * LDA + ii] = ok ? v3 : 0.f;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) As[(p * BKG + rr) * LDA + ii] = ok ? av[p] : 0.f;
     }
 #pragma unroll
     for (int j = 0; j < NEB; ++j) {
@@ -949,17 +988,8 @@ constexpr int kRT = 512;            // 8 waves
 constexpr int kRBN = 128;          // block columns (B slice resident in LDS)
 constexpr int kRGridCap = 256;      // one workgroup per CU (LDS-bound)
 
-template <int AM>
-constexpr int rg_planes() {
-  return (AM == A_FWD || AM == A_S3) ? 3
-         : ((AM == A_S1MUL || AM == A_FWD2 || AM == A_S2) ? 2 : ((AM == A_U || AM == A_RAW1) ? 1 : 0));
-}
-
 bool rgemm_shape(int K, int N) { return K % 64 == 0 && K <= 256 && N % kRBN == 0; }
 
-// V (schedule variant, A/B): 0 = Bt b128 reads, compiler schedule; 1 = + one fenced region per tile
-// (prefetch one tile ahead); 2 = + loads / layer-1 VALU interleaved one per MFMA; 3 = Bs[k][n] with one
-// ds_read_b32 per k-step and column tile, compiler schedule.
 // BNC = block columns: 128 for the W x W layers; 64 for the output layer (N = out_features <= 64, one
 // column block, columns past N zero in the staged B and never stored; E_OUT reduces a row's outputs
 // inside one wave, E_SEEDS writes the seeds and the bias-gradient column sums).
@@ -970,7 +1000,7 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
   static_assert((NI == 2 || NI == 4) && WGN >= 1 && WGN * WGM == NW, "rgemm wave grid");
   static_assert((EM != E_OUT && EM != E_OUT_SEEDS1) || WGN == 1, "E_OUT reduces each row inside one wave");
   constexpr bool L1 = a_is_l1<AM>();
-  constexpr int NV = rg_planes<AM>();
+  constexpr int NV = a_planes<AM>();
   constexpr int SK = L1 ? k1_stride<D>() : 1;
   constexpr int NP = (EM == E_ACT_BWD || EM == E_SEEDS || EM == E_OUT_SEEDS1) ? 1 : 0;
   static_assert(!L1 || D > 0, "layer-1 modes need D");
@@ -1002,7 +1032,7 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
     }
     Bt[n * Kp + k] = v;
   }
-  if constexpr (L1) {
+  if constexpr (L1) {  // stage_k1t, written out: the call changes the d = 2, 4 kernels' code
     for (int e = tid; e < K * SK; e += NT) {
       const int k = e / SK, i = e - k * SK;
       k1s[e] = i < D ? a.k1[i * K + k] : (i == D ? a.b1[k] : 0.f);
@@ -1098,47 +1128,28 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          const float z = zt[q], zy = yt[q];
-          const float h = ftanh(z), s1 = 1.f - h * h;
+          float v[AM == A_L1F ? S : 2];
+          l1_streams(v, zt[q], yt[q]);
           if constexpr (AM == A_L1F) {
-            at[0][q] = h;
-            at[1][q] = s1 * zy;
-            if constexpr (S > 2) at[S - 1][q] = -2.f * h * s1 * zy * zy;
-          } else {
-            at[0][q] = s1 * zy;
+            at[0][q] = v[0];
+            at[1][q] = v[1];
+            if constexpr (S > 2) at[2][q] = v[2];
+          } else {  // A_L1A: abar1 = s1 zy, stream 1 of the same
+            at[0][q] = v[1];
           }
         }
       }
 #pragma unroll
       for (int s = 0; s < 16; ++s) {
-        float av[3];
+        float av[S];
         if constexpr (L1) {
 #pragma unroll
           for (int si = 0; si < S; ++si) av[si] = at[si][s];
-        } else if constexpr (AM == A_FWD) {
-          const float h = t[0][s], zd = t[1][s], zdd = t[2][s];
-          const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-          av[0] = h;
-          av[1] = s1 * zd;
-          av[2] = fmaf(s1, zdd, s2 * zd * zd);
-        } else if constexpr (AM == A_S1MUL) {
-          const float h = t[0][s];
-          av[0] = (1.f - h * h) * t[1][s];
-        } else if constexpr (AM == A_U) {
-          av[0] = 2.f * t[0][s];
-        } else if constexpr (AM == A_RAW1) {
-          av[0] = t[0][s];
-        } else if constexpr (AM == A_FWD2) {
-          const float h = t[0][s];
-          av[0] = h;
-          av[1] = (1.f - h * h) * t[1][s];
-        } else if constexpr (AM == A_S2) {
-          av[0] = t[0][s];
-          av[1] = t[1][s];
-        } else {  // A_S3
-          av[0] = t[0][s];
-          av[1] = t[1][s];
-          av[2] = t[2][s];
+        } else {
+          float pv[NV];
+#pragma unroll
+          for (int p = 0; p < NV; ++p) pv[p] = t[p][s];
+          a_operand<AM, S>(pv, av);
         }
 #pragma unroll
         for (int si = 0; si < S; ++si)
@@ -1185,20 +1196,15 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
           const int r = r0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * hi;
           const bool ok = (!CHECK || r < a.R) && nv;
           const uint32_t o = (uint32_t)(r * N + n);
+          [[maybe_unused]] constexpr int s1i = S > 1 ? 1 : 0;  // the streams an S < 3 mode lacks repeat stream 0
           if constexpr (EM == E_ACT_FWD) {
-            if (ok) {
-              sto(a.po0, o, ftanh(acc[0][ni][q] + bn));
-              sto(a.po1, o, acc[1][ni][q]);
-              if constexpr (S > 2) sto(a.po2, o, acc[S - 1][ni][q]);
-            }
+            if (ok) epi_act_fwd<S>(a, o, acc[0][ni][q], acc[s1i][ni][q], acc[S - 1][ni][q], bn);
           } else if constexpr (EM == E_STORE) {
-            if (ok) sto(a.po0, o, acc[0][ni][q]);
-          } else if constexpr (EM == E_STORE3) {  // hbar1 (R2b), read once by l1_grad_kernel
-            if (ok) {
-              sto_h(a.po0, o, acc[0][ni][q]);
-              sto_h(a.po1, o, acc[1][ni][q]);
-              if constexpr (S > 2) sto_h(a.po2, o, acc[S - 1][ni][q]);
-            }
+            if (ok) epi_store<S, CP_DEFAULT>(a, o, acc[0][ni][q], acc[s1i][ni][q], acc[S - 1][ni][q]);
+          } else if constexpr (EM == E_STORE3) {
+            // the hbar1 planes (R2b), read once by l1_grad_kernel: streaming stores, l1_grad 3.79 -> 3.60 ms,
+            // R2b 13.61 -> 13.49 ms (profiles/r05_c5_nt_hb1_ab.txt)
+            if (ok) epi_store<S, CP_STREAM>(a, o, acc[0][ni][q], acc[s1i][ni][q], acc[S - 1][ni][q]);
           } else if constexpr (EM == E_OUT_SEEDS1) {
             if (ok) {
               const float y = acc[0][ni][q] + bn, yd = acc[1][ni][q];
@@ -1212,15 +1218,7 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
               pacc[ni] += yb;
             }
           } else if constexpr (EM == E_OUT) {
-            if (ok) {
-              const float y = acc[0][ni][q] + bn, yd = acc[1][ni][q], ydd = acc[2][ni][q];
-              sto(a.po0, o, y);
-              sto(a.po1, o, yd);
-              sto(a.po2, o, ydd);
-              t0[q] = fmaf(y, y, t0[q]);
-              t1[q] = fmaf(y, yd, t1[q]);
-              t2[q] = fmaf(yd, yd, fmaf(y, ydd, t2[q]));
-            }
+            if (ok) epi_out(a, o, acc[0][ni][q], acc[1][ni][q], acc[2][ni][q], bn, t0[q], t1[q], t2[q]);
           } else if constexpr (EM == E_SEEDS) {
             if (ok) {
               const float ub = acc[0][ni][q];
@@ -1259,15 +1257,8 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
       if constexpr (EM == E_OUT || EM == E_OUT_SEEDS1) {  // per-row reductions over the 32 lanes of each half-wave
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-          float p0 = t0[q], p1 = t1[q], p2 = t2[q];
-#pragma unroll
-          for (int off = 16; off > 0; off >>= 1) {
-            p0 += __shfl_xor(p0, off, 64);
-            p1 += __shfl_xor(p1, off, 64);
-            p2 += __shfl_xor(p2, off, 64);
-          }
           const int r = r0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * hi;
-          if (l31 == 0 && r < a.R) a.terms[r] = make_float4(2.f * p1, 2.f * p2, p0, 0.f);
+          out_row_terms<32>(a, 0, r, t0[q], t1[q], t2[q]);
         }
       }
     };
@@ -1299,8 +1290,6 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
   }
 }
 
-// NPR = 2 (first-order chunks, GB_PL): only the pairs (h, zbar) and (s1 z', z'bar); the z'' and adjoint pairs are
-// zero there, so their planes (and, GA_L1, abar0) are not read.
 // rgemm16: the output layer (K = W <= 256, N = out_features <= 48) on v_mfma_f32_16x16x4_f32 — 16-column tiles, so
 // 40 outputs take 48 MFMA columns instead of rgemm's 64 (the product was MFMA-bound on that padding). Same B-resident
 // scheme as rgemm (the K x 48 slice of Ko in LDS once per workgroup, Bt[n][k], pitch K + 4), 8 waves of 32 rows x 48
@@ -1312,7 +1301,7 @@ __global__ __launch_bounds__(NW * 64, 1) void rgemm(GemmArgs a) {
 template <int S, int AM, int EM>
 __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
   constexpr int NT = 3, BNC = 16 * NT, MI = 2, NW = kRT / 64, BMR = 32 * NW;
-  constexpr int NV = rg_planes<AM>();
+  constexpr int NV = a_planes<AM>();
   static_assert(EM == E_OUT || EM == E_SEEDS || EM == E_OUT_SEEDS1, "rgemm16: output-layer epilogues");
   static_assert(NV >= 1 && !a_is_l1<AM>(), "rgemm16: plane operands");
   constexpr int NP = (EM == E_SEEDS || EM == E_OUT_SEEDS1) ? 1 : 0;
@@ -1373,23 +1362,13 @@ __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
         }
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float av[MI][3];
+        float av[MI][S];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
-          if constexpr (AM == A_FWD) {
-            const float h = t[0][mi][j], zd = t[1][mi][j], zdd = t[2][mi][j];
-            const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-            av[mi][0] = h;
-            av[mi][1] = s1 * zd;
-            av[mi][2] = fmaf(s1, zdd, s2 * zd * zd);
-          } else if constexpr (AM == A_FWD2) {
-            const float h = t[0][mi][j];
-            av[mi][0] = h;
-            av[mi][1] = (1.f - h * h) * t[1][mi][j];
-          } else {  // A_S1MUL
-            const float h = t[0][mi][j];
-            av[mi][0] = (1.f - h * h) * t[1][mi][j];
-          }
+          float pv[NV];
+#pragma unroll
+          for (int p = 0; p < NV; ++p) pv[p] = t[p][mi][j];
+          a_operand<AM, S>(pv, av[mi]);
         }
 #pragma unroll
         for (int s = 0; s < S; ++s)
@@ -1401,7 +1380,7 @@ __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
       }
     };
     // register double buffer, loads unconditional (the last prefetch reads the next block's tile 0), one fenced
-    // scheduling region per tile (rgemm's V = 1 schedule)
+    // scheduling region per tile (as in rgemm)
     __builtin_amdgcn_sched_barrier(0);
     for (int kt = 0; kt < nk; kt += 2) {
       load_tile(t1, kt + 1, mb);
@@ -1427,15 +1406,8 @@ __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
           const bool ok = r < a.R && nv;
           const uint32_t o = (uint32_t)(r * N + n);
           if constexpr (EM == E_OUT) {
-            if (ok) {
-              const float y = acc[0][mi][nt][i] + bn, yd = acc[1][mi][nt][i], ydd = acc[2][mi][nt][i];
-              sto(a.po0, o, y);
-              sto(a.po1, o, yd);
-              sto(a.po2, o, ydd);
-              tr0[i] = fmaf(y, y, tr0[i]);
-              tr1[i] = fmaf(y, yd, tr1[i]);
-              tr2[i] = fmaf(yd, yd, fmaf(y, ydd, tr2[i]));
-            }
+            if (ok)
+              epi_out(a, o, acc[0][mi][nt][i], acc[1][mi][nt][i], acc[2][mi][nt][i], bn, tr0[i], tr1[i], tr2[i]);
           } else if constexpr (EM == E_OUT_SEEDS1) {
             if (ok) {
               const float y = acc[0][mi][nt][i] + bn, yd = acc[1][mi][nt][i];
@@ -1465,15 +1437,8 @@ __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
       if constexpr (EM == E_OUT || EM == E_OUT_SEEDS1) {  // per-row sums over the 16 lanes of the q-group
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          float p0 = tr0[i], p1 = tr1[i], p2 = tr2[i];
-#pragma unroll
-          for (int off = 8; off > 0; off >>= 1) {
-            p0 += __shfl_xor(p0, off, 64);
-            p1 += __shfl_xor(p1, off, 64);
-            p2 += __shfl_xor(p2, off, 64);
-          }
           const int r = r0 + wave * 32 + mi * 16 + 4 * qg + i;
-          if (l16 == 0 && r < a.R) a.terms[r] = make_float4(2.f * p1, 2.f * p2, p0, 0.f);
+          out_row_terms<16>(a, 0, r, tr0[i], tr1[i], tr2[i]);
         }
       }
     }
@@ -1498,10 +1463,11 @@ __global__ __launch_bounds__(kRT, 1) void rgemm16(GemmArgs a) {
   }
 }
 
+// NPR = 2 (first-order chunks, GB_PL): only the pairs (h, zbar) and (s1 z', z'bar); the z'' and adjoint pairs are
+// zero there, so their planes (and, GA_L1, abar0) are not read.
 template <int MI, int NI, int GA, int GB, int D = 0, int NPR = 4>
 __global__ __launch_bounds__(kRT, 1) void wgrad2(WgradArgs a) {
   static_assert(GA != GA_L1 || D > 0, "GA_L1 needs D");
-  static_assert(GA != GA_RAW4, "wgrad2: A streams from planes (GA_PL) or rows (GA_L1)");
   static_assert(NPR == 4 || (NPR == 2 && GB == GB_PL), "wgrad2: 4 stream pairs, or 2 on the first-order chain");
   constexpr int NVA = GA == GA_PL ? NPR : 0;                 // raw A planes per feature group
   constexpr int NVB = NPR == 2 ? 2 : (GB == GB_PL ? 5 : 4);  // raw B planes per column group
@@ -1563,7 +1529,7 @@ __global__ __launch_bounds__(kRT, 1) void wgrad2(WgradArgs a) {
   };
   auto step = [&](const Regs& g, int64_t rb0) {
     const bool ok = rb0 + hi < rs1;
-    float av[MI][4], bv[NI][4];
+    float av[MI][NPR], bv[NI][NPR];
     [[maybe_unused]] float xv[GA == GA_L1 ? NXP : 1];
     if constexpr (GA == GA_L1) {  // through the wave's slab (LDS ops of one wave complete in order)
       __builtin_amdgcn_wave_barrier();  // the previous step's cross-lane reads of the slab stay before these stores
@@ -1583,24 +1549,11 @@ __global__ __launch_bounds__(kRT, 1) void wgrad2(WgradArgs a) {
     for (int mi = 0; mi < MI; ++mi) {
       if constexpr (GA == GA_L1) {
         const float z = kc[mi][D] + dotd<D>(xv, kc[mi]), zd = dotd<D>(xv + D, kc[mi]);
-        const float h = ftanh(z), s1 = 1.f - h * h;
-        av[mi][0] = h;
-        av[mi][1] = s1 * zd;
-        if constexpr (NPR > 2) {
-          const float zb = dotd<D>(xv + 2 * D, kc[mi]);
-          av[mi][2] = -2.f * h * s1 * zd * zd;
-          av[mi][3] = s1 * zb;
-        }
+        float zb = 0.f;
+        if constexpr (NPR > 2) zb = dotd<D>(xv + 2 * D, kc[mi]);
+        l1_streams(av[mi], z, zd, zb);
       } else {
-        const float h = g.ra[mi][0], zd = g.ra[mi][1];
-        const float s1 = 1.f - h * h, s2 = -2.f * h * s1;
-        av[mi][0] = h;
-        av[mi][1] = s1 * zd;
-        if constexpr (NPR > 2) {
-          const float zdd = g.ra[mi][2], zeb = g.ra[mi][3];
-          av[mi][2] = fmaf(s1, zdd, s2 * zd * zd);
-          av[mi][3] = s1 * zeb;
-        }
+        fwd_streams(g.ra[mi], av[mi]);
       }
 #pragma unroll
       for (int p = 0; p < NPR; ++p) av[mi][p] = ok ? av[mi][p] : 0.f;  // rows past the slice add nothing
@@ -1710,6 +1663,7 @@ __global__ __launch_bounds__(kT) void wgrad_o(WgradArgs a) {
   };
   auto step = [&](const Regs& g, int64_t rb) {
     const bool ok = rb + rq < rs1;  // rows past the slice add nothing
+    // fwd_streams, written out: the helper changes this kernel's code and register counts
     float av[FI][4];
 #pragma unroll
     for (int fi = 0; fi < FI; ++fi) {
