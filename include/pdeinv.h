@@ -47,7 +47,9 @@ extern "C" {
 
 #define PDEINV_ABI_VERSION 10  /* 10: pdeinv_sde_simulate_mf_kmv; 9: pdeinv_ou_exact_sample, pdeinv_kmv_mlp_path */
 /* Added within version 10 (new entry points only, nothing existing changed): pdeinv_realnvp_time_derivs,
- * pdeinv_realnvp_time_derivs_sets, pdeinv_realnvp_time_impl, pdeinv_kmv_weights_from_ds(_workspace_bytes). */
+ * pdeinv_realnvp_time_derivs_sets, pdeinv_realnvp_time_impl, pdeinv_kmv_weights_from_ds(_workspace_bytes);
+ * PDEINV_POT_MLP, pdeinv_mlp_shape, pdeinv_mlp_potential(_path, _workspace_bytes),
+ * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes). */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -71,7 +73,10 @@ typedef enum {
      all-reduce -> pdeinv_mf_mean_path), or update by update with pdeinv_mf_step. */
   PDEINV_POT_MEANFIELD_QUADRATIC = 2,
   /* U = 0 (core/potential.py VoidPotential). */
-  PDEINV_POT_NONE = 3
+  PDEINV_POT_NONE = 3,
+  /* The learned V_hypothesis MLP (core/model.py:32-62), parameters on the device: accepted by
+     pdeinv_sde_simulate_mlp only (every other simulator entry point rejects it as an unknown kind). */
+  PDEINV_POT_MLP = 4
 } pdeinv_potential_kind;
 
 typedef struct {
@@ -532,6 +537,47 @@ int pdeinv_fp_exact_sample(int64_t n, int32_t dim, uint64_t seed, uint32_t count
 int pdeinv_gmm_potential(int32_t dim, int32_t n_centers, float sigma, const float* mus_host,
                          const float* d_x, int64_t n, int64_t ld, float* d_value,
                          float* d_grad, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The learned potential V_theta = V_hypothesis (core/model.py:32-62: n_layers tanh layers of `width`,
+ * Dense(out_features), sum of squares) as a batch function and as the simulator's potential.
+ * d_params: the DEVICE flat flax vector [K_1, b_1, ..., K_o, b_o] (pdeinv_mlp_param_count floats) — the
+ * trainer's live parameter buffer, read on the caller's stream (no host copy, no synchronisation; the
+ * per-call weight image is built by a small device kernel).
+ *
+ * pdeinv_mlp_potential — the MLP analogue of pdeinv_gmm_potential: d_value[r] = V(x_r), d_grad[r*dim + k] =
+ * d_k V(x_r) for rows x_r = d_x + r*ld (ld 0 => dim; ld < dim: INVALID). Either output nullable; n == 0 is a
+ * no-op. What the reference's "relative error of gradient estimation initial / terminal" needs
+ * (methods/consistency_instances/kinetic_fokker_planck.py:81-91). The shape selects the path
+ * (pdeinv_mlp_potential_path):
+ *   2  the 16-row MFMA tile (dim <= 8, width <= 20 zero-padded, 1 <= n_layers <= 8, any out_features): the
+ *      forward / reverse device code of pdeinv_sde_simulate_mlp's drift, so this is its direct test;
+ *   1  any other shape inside pdeinv_mlp_fused_supported: rows [x | 0] through the fused fp32-MFMA residual
+ *      kernels in their gradient-only mode (the value is the V slot of their per-row terms, which both chains
+ *      write before the gradient-only return);
+ *   0  unsupported (PDEINV_ERR_UNSUPPORTED). A shape with a field < 1 is PDEINV_ERR_INVALID.
+ * Workspace: pdeinv_mlp_potential_workspace_bytes(shape, n), 256-byte aligned. Deterministic.
+ *
+ * pdeinv_sde_simulate_mlp — the contract of pdeinv_sde_simulate (utils/sampling_utils.py:6-52) with
+ * grad U = grad V_theta: the same tau0 shift stream and Philox noise stream (global ids particle_offset + i,
+ * update s uses counter_offset + s), d_noise / d_shift_u honoured, traj time-major, tau = tau0 + s*dt, last =
+ * the state after the final update, every output nullable, deterministic (no atomics; a particle's numbers
+ * depend on its global id and its row only, so any sharding over calls gives the same bits). Requires
+ * desc->potential.kind == PDEINV_POT_MLP (else INVALID; potential.params is ignored) and desc->dim ==
+ * shape->dim. Only the tile envelope is supported (pdeinv_sde_simulate_mlp_supported; else UNSUPPORTED).
+ * Fused moments are not offered: take pdeinv_moments of the outputs.
+ * Workspace: pdeinv_sde_simulate_mlp_workspace_bytes, 256-byte aligned.
+ * --------------------------------------------------------------------------------------- */
+typedef struct { int32_t dim, n_layers, width, out_features; } pdeinv_mlp_shape;
+int pdeinv_mlp_potential_path(const pdeinv_mlp_shape* shape);
+size_t pdeinv_mlp_potential_workspace_bytes(const pdeinv_mlp_shape* shape, int64_t n);
+int pdeinv_mlp_potential(const pdeinv_mlp_shape* shape, const float* d_params, const float* d_x, int64_t n,
+                         int64_t ld, float* d_value, float* d_grad, void* d_workspace, void* stream);
+int pdeinv_sde_simulate_mlp_supported(const pdeinv_mlp_shape* shape);
+size_t pdeinv_sde_simulate_mlp_workspace_bytes(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape);
+int pdeinv_sde_simulate_mlp(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape, const float* d_params,
+                            const float* d_z0, float* d_traj, float* d_tau, float* d_last, void* d_workspace,
+                            void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Exact Gaussian sampler — core/distribution.py:52-65 Gaussian.sample: z = C^{1/2} xi + mu.

@@ -92,6 +92,39 @@ class MeanFieldQuadraticPotential(Potential):
         return dict(kind=native.POT_MEANFIELD_QUADRATIC, params=self.A.ravel())
 
 
+class MLPPotential(Potential):
+    """The learned V_theta = V_hypothesis (core/model.py:32-62) as a potential: `model` a core.model.V_hypothesis,
+    `params` its param tree (device tensors). The flat device vector is rebuilt from the tree at every use, so a
+    tree whose tensors the trainer updates in place is always read live. value / gradient over batches and the
+    simulator's drift all run the native MLP kernels (utils.native.mlp_potential / sde_simulate_mlp)."""
+
+    def __init__(self, model, params):
+        if getattr(model, "residual_kind", None) != "mlp":
+            raise ValueError("MLPPotential takes a core.model.V_hypothesis")
+        self.model = model
+        self.params = params
+        self.dim = int(params["params"]["layers_0"]["kernel"].shape[0])
+
+    def dims(self):
+        return self.model.dims(self.dim)
+
+    def flat(self) -> torch.Tensor:
+        return self.model.flat(self.params)
+
+    def value(self, x: torch.Tensor):
+        single = x.dim() == 1
+        v, _ = native.mlp_potential(self.dims(), self.flat(), x.reshape(-1, self.dim), True, False)
+        return v[0] if single else v
+
+    def gradient(self, x: torch.Tensor):
+        single = x.dim() == 1
+        _, g = native.mlp_potential(self.dims(), self.flat(), x.reshape(-1, self.dim), False, True)
+        return g[0] if single else g
+
+    def native_desc(self) -> dict:
+        return dict(kind=native.POT_MLP, dims=self.dims(), params=self.flat())
+
+
 def resolve(potential_grad) -> Potential:
     """Accept a Potential or its bound `.gradient` (what the reference passes, …_GMM.py:120)."""
     if isinstance(potential_grad, Potential):

@@ -368,6 +368,75 @@ extern "C" int64_t pdeinv_mlp_param_count(int32_t dim, int32_t n_layers, int32_t
   return n + (int64_t)width * out_features + out_features;
 }
 
+// ---- pdeinv_mlp_potential outside the tile envelope (sde_mlp.hip) ---------------------------------------
+// Rows [x | 0] of row_dim() coordinates through the fused engine in RowMode::GRAD_ONLY, chunk by chunk: grad V is
+// grad_rows(), V is terms[r].z — run_chunk_l1 and run_chunk_full both write the terms plane (E_OUT, sum_terms)
+// before their grad_only return.
+__global__ void mlp_pot_rows_kernel(const float* __restrict__ x, int64_t ld, int64_t R, int D, int Dp,
+                                    float* __restrict__ dst) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= R * 2 * Dp) return;
+  const int64_t r = q / (2 * Dp);
+  const int c = (int)(q - r * 2 * Dp);
+  dst[q] = c < D ? x[r * ld + c] : 0.f;
+}
+__global__ void mlp_pot_out_kernel(const float* __restrict__ G, const float4* __restrict__ terms, int64_t R, int D,
+                                   int Dp, float* __restrict__ value, float* __restrict__ grad) {
+  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= R * D) return;
+  const int64_t r = q / D;
+  const int k = (int)(q - r * D);
+  if (grad) grad[q] = G[r * Dp + k];
+  if (value && k == 0) value[r] = terms[r].z;
+}
+
+namespace {
+constexpr int64_t kPotChunk = 1 << 16;
+pdeinv_kfp_mlp_desc pot_desc(const pdeinv_mlp_shape* s, int64_t n) {
+  pdeinv_kfp_mlp_desc m{};
+  m.dim = s->dim; m.n_layers = s->n_layers; m.width = s->width; m.out_features = s->out_features;
+  m.impl = PDEINV_MLP_IMPL_AUTO;
+  m.chunk_rows = n < 1 ? 1 : (n < kPotChunk ? n : kPotChunk);
+  return m;
+}
+}  // namespace
+
+size_t pdeinv::mlp_rows_potential_workspace_bytes(const pdeinv_mlp_shape* s, int64_t n) {
+  const pdeinv_kfp_mlp_desc m = pot_desc(s, n);
+  FusedShape f;
+  if (!fused_shape(&m, &f)) return 0;
+  const FusedEngine eng(m, f, true, "mlp_potential");
+  return sizeof(float) * (eng.ws_floats() + (((size_t)m.chunk_rows * 2 * f.Dp + 63) & ~(size_t)63));
+}
+
+int pdeinv::mlp_rows_potential(const pdeinv_mlp_shape* s, const float* params, const float* x, int64_t n, int64_t ld,
+                               float* value, float* grad, void* ws, hipStream_t st) {
+  const pdeinv_kfp_mlp_desc m = pot_desc(s, n);
+  FusedShape f;
+  PDEINV_REQUIRE(fused_shape(&m, &f), PDEINV_ERR_UNSUPPORTED, "mlp_potential: shape outside the fused row envelope");
+  FusedEngine eng(m, f, true, "mlp_potential");
+  float* w = (float*)ws;
+  float* rows = w + eng.ws_floats();
+  int rc = eng.begin(params, nullptr, w, nullptr, st);
+  if (rc) return rc;
+  const int D = s->dim, Dp = f.Dp;
+  MlpLossArgs la{};
+  la.d = Dp;
+  for (int64_t r0 = 0; r0 < n; r0 += m.chunk_rows) {
+    const int64_t R = n - r0 < m.chunk_rows ? n - r0 : m.chunk_rows;
+    const int64_t nq = R * 2 * Dp;
+    hipLaunchKernelGGL(mlp_pot_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, x + r0 * ld, ld, R, D,
+                       Dp, rows);
+    rc = eng.chunk(rows, 2 * Dp, R, la, RowMode::GRAD_ONLY, nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mlp_pot_out_kernel, dim3((unsigned)((R * D + 255) / 256)), dim3(256), 0, st, eng.grad_rows(),
+                       mlpf::term_rows(eng.c), R, D, Dp, value ? value + r0 : nullptr, grad ? grad + r0 * D : nullptr);
+    rc = check_launch("mlp_pot_out_kernel");
+    if (rc) return rc;
+  }
+  return PDEINV_OK;  // no end(): a gradient-only run has no parameter gradient to unpad
+}
+
 // ---- KFP residual (config C5) --------------------------------------------------------------------
 extern "C" int pdeinv_residual_kfp_mlp(const pdeinv_kfp_mlp_desc* d, const float* zi, int64_t ni, int64_t ldi,
                                        const float* zt, int64_t nt, int64_t ldt, const float* z0, int64_t n0,

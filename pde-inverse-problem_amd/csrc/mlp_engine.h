@@ -68,6 +68,12 @@ struct RowEngine {
   virtual int end() = 0;
 };
 
+// pdeinv_mlp_potential outside the 16-row tile envelope (sde_mlp.hip): rows [x | 0] through the fused engine in
+// RowMode::GRAD_ONLY; grad V from grad_rows(), V from the terms plane (mlp.hip). ld >= dim; either output nullable.
+size_t mlp_rows_potential_workspace_bytes(const pdeinv_mlp_shape* s, int64_t n);
+int mlp_rows_potential(const pdeinv_mlp_shape* s, const float* params, const float* x, int64_t n, int64_t ld,
+                       float* value, float* grad, void* ws, hipStream_t st);
+
 // who: the entry point's name in error messages ("kfp_mlp" / "kmv_mlp")
 std::unique_ptr<RowEngine> make_library_engine(const pdeinv_kfp_mlp_desc& m, const char* who);
 

@@ -45,6 +45,9 @@ struct Chunk {
 
 // g = grad_x V [R x d] of the last run_chunk (workspace view)
 const float* grad_rows(const Chunk& c);
+// terms[r] = {V', V'', V, 0} of the last run_chunk's rows (workspace view). Both chains write the plane (the output
+// layer's E_OUT epilogue and sum_terms) before a grad_only chunk returns, so it is valid in every mode.
+const float4* term_rows(const Chunk& c);
 
 int run_chunk(const Chunk& c, const LossHook& loss, hipStream_t st);
 

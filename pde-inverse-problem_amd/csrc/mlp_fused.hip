@@ -1918,6 +1918,7 @@ static Layout layout(int d, int L, int W, int O, int64_t Bc) {
 size_t workspace_floats(int d, int L, int W, int O, int64_t Bc) { return layout(d, L, W, O, Bc).total; }
 
 const float* grad_rows(const Chunk& c) { return c.ws + layout(c.d, c.L, c.W, c.O, c.Bc).g; }
+const float4* term_rows(const Chunk& c) { return (const float4*)(c.ws + layout(c.d, c.L, c.W, c.O, c.Bc).terms); }
 
 // zero the first n floats of every plane and the first ng floats of g (first_order chunks)
 static int zero_planes(const std::vector<float*>& planes, size_t n, float* g, size_t ng, hipStream_t st) {

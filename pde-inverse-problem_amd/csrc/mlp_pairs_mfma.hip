@@ -40,31 +40,17 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mlp_tile.h"  // kW, kNS, kLMax, the P-layout helpers, the image plan
 
 namespace pdeinv {
 namespace mlpq {
 
-constexpr int kW = 20;       // padded hidden width
-constexpr int kNS = 5;       // compact slots of a hidden stream
-constexpr int kLMax = 8;     // hidden (tanh) layers
-constexpr int kWaves = 8;    // waves per block of pass 1 (two blocks per CU)
+constexpr int kWaves = 8;   // waves per block of pass 1 (two blocks per CU)
 constexpr int kWaves2 = 4;   // waves per block of pass 2: one per SIMD (512 registers: the checkpoints stay in registers)
 constexpr int kChunk = 256;  // references per work unit (16 tiles)
 constexpr int kPS = 28;      // LDS image row pitch (floats); odd rows shifted by one 16-byte chunk (img_at)
 constexpr int kRowsA = 48, kRowsB = 32;
 constexpr int kTImg = (kRowsA + kRowsB) * kPS;  // floats per wave: the [A | B] transpose images
-
-// feature carried by compact slot k in lane group g, for a stream of ns slots
-__host__ __device__ inline int slot_feat(int ns, int k, int g) {
-  const int fm = ns / 4;
-  return k < 4 * fm ? 16 * (k >> 2) + 4 * g + (k & 3) : 16 * fm + 4 * (k - 4 * fm) + g;
-}
-// feature of M row r of block mb (-1: a padding row)
-__host__ __device__ inline int row_feat(int ns, int mb, int r) {
-  const int fm = ns / 4;
-  if (mb < fm) return 16 * mb + r;
-  return (r & 3) < ns % 4 ? 16 * fm + 4 * (r & 3) + (r >> 2) : -1;
-}
 
 struct Args {
   int L, D, n_ch;
@@ -85,31 +71,10 @@ struct Args {
   float* aslab;           // pass 2: [n_waves][8]
 };
 
-__device__ __forceinline__ float ftanh(float z) {
-  const float e = __builtin_amdgcn_exp2f(2.8853900817779268f * z);
-  return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-__device__ __forceinline__ f32x4 mfma(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 outer products; lane 4b + j, register i of the result
 // is block b's A[lane 4b + i] * B[lane 4b + j] (tools/mfma4_probe.hip; ~0.7 of the 16x16x4 issue rate)
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 0, 0, 0);
-}
-
-
-// N consecutive 64-lane units of the image starting at unit u0 (u0 % 4 == 0): 16-B reads
-template <int N>
-__device__ __forceinline__ void load_units(const float* img, int u0, int lane, float (&w)[N]) {
-  static_assert(N % 4 == 0, "units come in fours");
-  const f32x4* q = reinterpret_cast<const f32x4*>(img) + (u0 >> 2) * 64 + lane;
-#pragma unroll
-  for (int c = 0; c < N / 4; ++c) {
-    const f32x4 v = q[c * 64];
-    w[4 * c] = v[0]; w[4 * c + 1] = v[1]; w[4 * c + 2] = v[2]; w[4 * c + 3] = v[3];
-  }
 }
 
 __device__ __forceinline__ int pos_of(int p) { return 4 * (p & 3) + (p >> 2); }
@@ -271,26 +236,6 @@ __device__ __forceinline__ void stream_of(const float (&h)[kNS], const float (&z
     else if constexpr (S == 1) H[k] = s1 * zu[k];
     else if constexpr (S == 2) H[k] = s1 * zv[k];
     else H[k] = fmaf(s1, zw[k], -2.f * h[k] * s1 * zv[k] * zv[k]);
-  }
-}
-
-// bias-initialised accumulators of a width-20 layer (slots 0..4 -> blocks 0 / 1)
-__device__ __forceinline__ void bias_hidden(const float* img, int boff, int g, f32x4 (&A)[2]) {
-  const float* b = img + boff;
-  A[0] = f32x4{b[4 * g], b[4 * g + 1], b[4 * g + 2], b[4 * g + 3]};
-  A[1] = f32x4{b[16 + g], 0.f, 0.f, 0.f};
-}
-__device__ __forceinline__ void compact_hidden(const f32x4 (&A)[2], float (&z)[kNS]) {
-  z[0] = A[0][0]; z[1] = A[0][1]; z[2] = A[0][2]; z[3] = A[0][3]; z[4] = A[1][0];
-}
-
-// layer-0 lane values: dimension k = 4 kk + g of the lane's group (0 past D)
-template <int KD>
-__device__ __forceinline__ void lane_dims(const float* row, int D, int g, float (&x)[KD]) {
-#pragma unroll
-  for (int kk = 0; kk < KD; ++kk) {
-    const int k = 4 * kk + g;
-    x[kk] = k < D ? row[k] : 0.f;
   }
 }
 
@@ -764,19 +709,9 @@ __global__ void kmvq_gbar_reduce_kernel(const float* __restrict__ gpart, int64_t
 }
 
 // -------------------------------------------------------------------------------------------------
-// weight image: lane-linear A-operand fragments, unit u of a section at ((u >> 2) * 64 + lane) * 4 + (u & 3)
+// weight image (layout and plan: mlp_tile.h ImageArgs / image_plan)
 // -------------------------------------------------------------------------------------------------
-constexpr int kMaxSec = 2 * (kLMax + 1);
 constexpr int kOutRegion = (kW + 1) * kW + kW + 4;  // slab of the folded output layer: [21][20] | c0 sum h | sum c0
-struct ImageArgs {
-  int L, D, W, O, KD;
-  int nsec;
-  int sec_layer[kMaxSec], sec_bwd[kMaxSec], sec_mb[kMaxSec], sec_u0[kMaxSec], sec_units[kMaxSec];
-  int64_t roff[kLMax + 1];
-  int bias_off[kLMax + 1];
-  int h0_off;  // float offset of h0 (kW + 4 floats)
-  int units_total, img_floats;
-};
 
 // h0 = the last tanh layer's output at input 0 and y0 = K_L^T h0 + b (one block): the expansion point of
 // the folded output layer (h0y0 = [h0 (W) | y0 (O)], fp64 slots). h0 goes through the pair kernels' own
@@ -935,6 +870,13 @@ __global__ __launch_bounds__(256) void kmvq_out_post_kernel(const float* __restr
   for (int o = threadIdx.x; o < O; o += blockDim.x) gL[(int64_t)W * O + o] += (float)(ktg[o] + 2.0 * C0 * y0[o]);
 }
 
+int build_image(const ImageArgs& ia, const float* params, double* h0y0, float* img, hipStream_t st) {
+  hipLaunchKernelGGL(kmvq_h0_kernel, dim3(1), dim3(256), 0, st, ia, params, h0y0);
+  hipLaunchKernelGGL(kmvq_image_kernel, dim3((unsigned)((ia.img_floats + 255) / 256)), dim3(256), 0, st, ia, params,
+                     (const double*)h0y0, img);
+  return check_launch("kmvq_image_kernel");
+}
+
 }  // namespace mlpq
 
 // ---- host driver ------------------------------------------------------------------------------
@@ -961,33 +903,13 @@ struct QPlan {
 QPlan q_plan(const pdeinv_kmv_mlp_desc* d) {
   QPlan p{};
   const int L = d->n_layers;
-  p.KD = d->dim <= 4 ? 1 : 2;
+  {
+    const mlpq::ImagePlan ip = mlpq::image_plan(d->dim, L, d->width, d->out_features);
+    p.ia = ip.ia;
+    p.KD = ip.KD;
+    for (int l = 0; l <= L; ++l) { p.fwd[l] = ip.fwd[l]; p.bwd[l] = ip.bwd[l]; }
+  }
   mlpq::ImageArgs& ia = p.ia;
-  ia.L = L; ia.D = d->dim; ia.W = d->width; ia.O = d->out_features; ia.KD = p.KD;
-  // image sections: per layer forward then backward, each rounded to 4 units
-  int u = 0, ns = 0;
-  auto sec = [&](int l, int bwd, int ks, int mb) {
-    ia.sec_layer[ns] = l; ia.sec_bwd[ns] = bwd; ia.sec_mb[ns] = mb; ia.sec_u0[ns] = u;
-    ia.sec_units[ns] = ks * mb;
-    ++ns;
-    const int at = u;
-    u += (ks * mb + 3) & ~3;
-    return at;
-  };
-  for (int l = 0; l <= L; ++l) {
-    p.fwd[l] = sec(l, 0, l == 0 ? 2 : mlpq::kNS, 2);  // layer 0: KD <= 2 k-steps (zeros past KD); layer L: M
-    p.bwd[l] = l < L ? sec(l, 1, mlpq::kNS, l == 0 ? 1 : 2) : 0;
-  }
-  ia.nsec = ns;
-  ia.units_total = u;
-  int bf = u * 64;
-  for (int l = 0; l <= L; ++l) {
-    ia.bias_off[l] = bf;
-    bf += mlpq::kW + 4;  // layer L: c0 [20], |y0|^2
-  }
-  ia.h0_off = bf;
-  bf += mlpq::kW + 4;
-  ia.img_floats = (bf + 3) & ~3;
   // padded parameter layout of the gradient slab: K [pin][20] then b [20] for the tanh layers (row
   // pitch 20: 4 pitch = 16 mod 32), then the folded output layer's region (kOutRegion floats). The
   // pad map covers the tanh layers only (pm.L = L - 1); the output region goes through kmvq_out_post_kernel.
@@ -995,8 +917,7 @@ QPlan q_plan(const pdeinv_kmv_mlp_desc* d) {
   int64_t ro = 0, po = 0;
   for (int l = 0; l <= L; ++l) {
     const int din = l == 0 ? d->dim : d->width, dout = l == L ? d->out_features : d->width;
-    ia.roff[l] = ro;
-    p.pm.roff[l] = ro;
+    p.pm.roff[l] = ro;  // = ia.roff[l]
     p.pm.poff[l] = po;
     if (l < L) {  // rows: layer 0 its D inputs, the others the padded width (the kernels' bias row is 20)
       const int pin = l == 0 ? d->dim : mlpq::kW;
@@ -1105,10 +1026,7 @@ int kmvq_run(const pdeinv_kmv_mlp_desc* d, const float* z, int64_t set_stride, i
   int rc = PDEINV_OK;
   double* h0y0 = (double*)(w + p.off_h0);
   if (pass == 0) {
-    hipLaunchKernelGGL(mlpq::kmvq_h0_kernel, dim3(1), dim3(256), 0, st, p.ia, params, h0y0);
-    hipLaunchKernelGGL(mlpq::kmvq_image_kernel, dim3((unsigned)((p.ia.img_floats + 255) / 256)), dim3(256), 0, st,
-                       p.ia, params, (const double*)h0y0, (float*)(w + p.off_img));
-    rc = check_launch("kmvq_image_kernel");
+    rc = mlpq::build_image(p.ia, params, h0y0, (float*)(w + p.off_img), st);
     if (rc) return rc;
   }
   rc = p.KD == 1 ? q_launch<1>(a, p, st, pass) : q_launch<2>(a, p, st, pass);

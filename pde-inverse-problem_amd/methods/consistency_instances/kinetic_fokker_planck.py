@@ -183,6 +183,28 @@ def recover_drift_richardson(z0, F, gamma: float, T: float, n: int, seed: int, p
     return {"S_rich": (8 * S[4] - 6 * S[2] + S[1]) / 3, "S_rich1": 2 * S[2] - S[1], "S_n": S[1], "counter": ctr}
 
 
+def relative_gradient_error(forward_fn, params, pde_instance, rng, n: int = 10000) -> dict:
+    """The reference's quality metric of a learned potential (kinetic_fokker_planck.py:81-91, commented out there):
+    sqrt(mean |grad V_theta - grad V*|^2 / mean |grad V*|^2) over n samples of the initial and of the terminal
+    distribution (their position halves; the keys are prng.split(rng, 2), as :82). grad V_theta of the V_hypothesis
+    model is native.mlp_potential; grad V* the true potential's gradient. Returns 0-dim fp64 device tensors."""
+    model = resolve_model(forward_fn)
+    if model.residual_kind != "mlp":
+        raise NotImplementedError("relative_gradient_error: the non-parametric V_hypothesis model only")
+    d = pde_instance.dim
+    flat = model.flat(params)
+    k_i, k_t = prng.split(rng, 2)
+    out = {}
+    for name, dist_, key in (("initial", pde_instance.distribution_initial, k_i),
+                             ("terminal", pde_instance.distribution_terminal, k_t)):
+        x = dist_.sample(n, key)[:, :d]
+        _, g = native.mlp_potential(model.dims(d), flat, x, False, True)
+        gt = pde_instance.potential.gradient(x.contiguous()).double()
+        err = torch.mean(torch.sum((g.double() - gt) ** 2, -1)) / torch.mean(torch.sum(gt ** 2, -1))
+        out[f"relative error of gradient estimation {name}"] = torch.sqrt(err)
+    return out
+
+
 def test_fn(forward_fn, pde_instance, rng):
     return {}  # kinetic_fokker_planck.py:72-92 returns {}
 

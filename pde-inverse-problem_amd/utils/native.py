@@ -27,6 +27,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "_build", "libpdeinv.so")
 
 PDEINV_OK, PDEINV_ERR_INVALID, PDEINV_ERR_UNSUPPORTED, PDEINV_ERR_HIP = 0, -1, -2, -3
 POT_QUADRATIC, POT_GMM, POT_MEANFIELD_QUADRATIC, POT_NONE = 0, 1, 2, 3
+POT_MLP = 4  # the learned V_hypothesis: sde_simulate_mlp only
 MAX_DIM, MAX_PARAMS = 16, 256
 KFP_NOUT = 9
 KFP_SLOTS = ("loss", "loss ground truth", "grad_norm", "loss_nabla", "loss_Hessian",
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "pdeinv_sde_simulate_mf_next_workspace_bytes", "pdeinv_sde_simulate_mf_next", "pdeinv_ou_exact_sample",
     "pdeinv_realnvp_time_derivs", "pdeinv_realnvp_time_derivs_sets", "pdeinv_realnvp_time_impl",
     "pdeinv_kmv_weights_from_ds_workspace_bytes", "pdeinv_kmv_weights_from_ds",
+    "pdeinv_mlp_potential_path", "pdeinv_mlp_potential_workspace_bytes", "pdeinv_mlp_potential",
+    "pdeinv_sde_simulate_mlp_supported", "pdeinv_sde_simulate_mlp_workspace_bytes", "pdeinv_sde_simulate_mlp",
 )
 
 
@@ -79,6 +82,11 @@ class SdeDesc(ctypes.Structure):
                 ("counter_offset", ctypes.c_uint32), ("ld_z0", ctypes.c_int64),
                 ("potential", PotentialDesc), ("d_noise", ctypes.c_void_p),
                 ("d_shift_u", ctypes.c_void_p), ("d_meanfield", ctypes.c_void_p)]
+
+
+class MlpShape(ctypes.Structure):
+    _fields_ = [("dim", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("out_features", ctypes.c_int32)]
 
 
 class KfpQuadDesc(ctypes.Structure):
@@ -221,6 +229,12 @@ def lib():
         "pdeinv_gather_random_step": (i32, [P, i64, i32, i32, u64, u32, P, P, P]),
         "pdeinv_fp_rows": (i32, [P, i64, i64, i32, i32, P, P]),
         "pdeinv_fp_exact_sample": (i32, [i64, i32, u64, u32, i64, f32, f32, P, P, P, P, P, P, P, P]),
+        "pdeinv_mlp_potential_path": (ctypes.c_int, [P]),
+        "pdeinv_mlp_potential_workspace_bytes": (ctypes.c_size_t, [P, i64]),
+        "pdeinv_mlp_potential": (i32, [P, P, P, i64, i64, P, P, P, P]),
+        "pdeinv_sde_simulate_mlp_supported": (ctypes.c_int, [P]),
+        "pdeinv_sde_simulate_mlp_workspace_bytes": (ctypes.c_size_t, [P, P]),
+        "pdeinv_sde_simulate_mlp": (i32, [P, P, P, P, P, P, P, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -393,6 +407,79 @@ def sde_simulate_kfp_gmm(z0: torch.Tensor, n_steps: int, dt: float, gamma: float
         stream_handle())
     del p_host
     _check(rc, "pdeinv_sde_simulate_kfp_gmm")
+    return res
+
+
+def mlp_shape(dims) -> MlpShape:
+    """pdeinv_mlp_shape of dims = [d, W, ..., W, out] (equal hidden widths: V_hypothesis)."""
+    dims = [int(v) for v in dims]
+    if len(dims) < 3 or any(w != dims[1] for w in dims[1:-1]):
+        raise NotImplementedError("MLP potential: dims = [d, W, ..., W, out] with one hidden width (V_hypothesis)")
+    return MlpShape(dims[0], len(dims) - 2, dims[1], dims[-1])
+
+
+MLP_POTENTIAL_PATHS = {2: "tile_mfma", 1: "fused_rows_mfma", 0: "unsupported"}
+
+
+def mlp_potential_path(dims) -> int:
+    """2: the 16-row MFMA tile (the simulator's drift code); 1: rows through the fused fp32-MFMA residual
+    kernels (gradient-only mode); 0: unsupported. Needs no GPU."""
+    return int(lib().pdeinv_mlp_potential_path(ctypes.byref(mlp_shape(dims))))
+
+
+def _mlp_params(shape: MlpShape, params_flat: torch.Tensor):
+    P = lib().pdeinv_mlp_param_count(shape.dim, shape.n_layers, shape.width, shape.out_features)
+    if params_flat.numel() != P or not params_flat.is_contiguous():
+        raise ValueError(f"MLP potential: params must be a contiguous flat vector of {P} floats")
+    return _dev(params_flat, "params")
+
+
+def mlp_potential(dims, params_flat: torch.Tensor, x: torch.Tensor, value: bool = True, grad: bool = True):
+    """V_theta(x_r) and grad V_theta(x_r) of the V_hypothesis MLP (core/model.py:32-62) over the rows of x [n, d]
+    (unit inner stride, any row stride) — pdeinv_mlp_potential. params_flat: the device flat flax vector, read
+    on the current stream. Returns (value [n] or None, grad [n, d] or None)."""
+    _require_gpu()
+    shape = mlp_shape(dims)
+    d = shape.dim
+    pp = _mlp_params(shape, params_flat)
+    n = x.shape[0]
+    xp, _, ld = _rows(x, "x", d) if n > 0 else (None, 0, d)
+    v = torch.empty(n, device=x.device, dtype=torch.float32) if value else None
+    g = torch.empty((n, d), device=x.device, dtype=torch.float32) if grad else None
+    nbytes = lib().pdeinv_mlp_potential_workspace_bytes(ctypes.byref(shape), n)
+    ws = torch.empty(max(nbytes // 4, 64), device=x.device, dtype=torch.float32)
+    _check(lib().pdeinv_mlp_potential(ctypes.byref(shape), pp, xp, n, ld, _dev(v, "value"), _dev(g, "grad"),
+                                      _dev(ws, "workspace"), stream_handle()), "pdeinv_mlp_potential")
+    return v, g
+
+
+def sde_simulate_mlp(z0: torch.Tensor, n_steps: int, dt: float, gamma: float, dims, params_flat: torch.Tensor, *,
+                     seed: int, counter_offset: int = 0, particle_offset: int = 0, noise_scale: float = SQRT2,
+                     random_shift: bool = True, noise: Optional[torch.Tensor] = None,
+                     shift_u: Optional[torch.Tensor] = None, traj: bool = True, tau: bool = True,
+                     last: bool = True, out: Optional[dict] = None) -> dict:
+    """utils/sampling_utils.py:25-52 with grad U = grad V_theta, the learned V_hypothesis (pdeinv_sde_simulate_mlp):
+    sde_simulate's contract and streams, params_flat the device flat flax vector. Time-major traj [n, N, 2d]."""
+    _require_gpu()
+    shape = mlp_shape(dims)
+    desc, p_host, z0p = _sim_desc(z0, n_steps, dt, gamma, dict(kind=POT_MLP), seed, counter_offset, particle_offset,
+                                  noise_scale, random_shift, noise, shift_u)
+    if desc.dim != shape.dim:
+        raise ValueError(f"q0_p0 has d = {desc.dim}, the net takes d = {shape.dim}")
+    pp = _mlp_params(shape, params_flat)
+    if not lib().pdeinv_sde_simulate_mlp_supported(ctypes.byref(shape)):
+        ws = None  # the call below reports the envelope; nothing is launched
+        res = {} if out is None else out
+    else:
+        res = _sim_outputs({} if out is None else out, z0, n_steps, traj, tau, last)
+        nbytes = lib().pdeinv_sde_simulate_mlp_workspace_bytes(ctypes.byref(desc), ctypes.byref(shape))
+        ws = torch.empty(max(nbytes // 4, 64), device=z0.device, dtype=torch.float32)
+    rc = lib().pdeinv_sde_simulate_mlp(
+        ctypes.byref(desc), ctypes.byref(shape), pp, z0p, _dev(res.get("traj") if traj else None, "traj"),
+        _dev(res.get("tau") if tau else None, "tau"), _dev(res.get("last") if last else None, "last"),
+        _dev(ws, "workspace"), stream_handle())
+    del p_host
+    _check(rc, "pdeinv_sde_simulate_mlp")
     return res
 
 

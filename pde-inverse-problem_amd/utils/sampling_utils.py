@@ -16,7 +16,7 @@ from typing import Optional
 
 import torch
 
-from core.potential import MeanFieldQuadraticPotential, resolve
+from core.potential import MeanFieldQuadraticPotential, MLPPotential, resolve
 from utils import native
 from utils.prng import Key
 
@@ -35,6 +35,20 @@ def simulate(q0_p0: torch.Tensor, n_steps: int, dt: float, key: Key, potential_g
         return simulate_mean_field(q0_p0, n_steps, dt, key, pot, gamma_friction, particle_offset=particle_offset,
                                    counter_offset=counter_offset, noise_scale=noise_scale,
                                    random_shift=random_shift, noise=noise, traj=traj, tau=tau)
+    if isinstance(pot, MLPPotential):  # the learned V_hypothesis: its own simulator, moments from its outputs
+        if moments and not traj:
+            raise ValueError("simulate: moments of an MLPPotential ensemble are taken from the written trajectory "
+                             "(traj=True); the learned-potential simulator has no fused moments")
+        nd = pot.native_desc()
+        r = native.sde_simulate_mlp(q0_p0, n_steps, dt, gamma_friction, nd["dims"], nd["params"], seed=key.seed,
+                                    counter_offset=counter_offset, particle_offset=particle_offset,
+                                    noise_scale=noise_scale, random_shift=random_shift, noise=noise, shift_u=shift_u,
+                                    traj=traj, tau=tau, last=last or moments, out=out)
+        if moments:
+            m = q0_p0.shape[1]
+            r["moments"] = torch.stack([native.moments(q0_p0), native.moments(r["traj"].reshape(-1, m)),
+                                        native.moments(r["last"])])
+        return r
     return native.sde_simulate(q0_p0, n_steps, dt, gamma_friction, pot.native_desc(), seed=key.seed,
                                counter_offset=counter_offset, particle_offset=particle_offset,
                                noise_scale=noise_scale, random_shift=random_shift, noise=noise,
