@@ -49,7 +49,9 @@ extern "C" {
 /* Added within version 10 (new entry points only, nothing existing changed): pdeinv_realnvp_time_derivs,
  * pdeinv_realnvp_time_derivs_sets, pdeinv_realnvp_time_impl, pdeinv_kmv_weights_from_ds(_workspace_bytes);
  * PDEINV_POT_MLP, pdeinv_mlp_shape, pdeinv_mlp_potential(_path, _workspace_bytes),
- * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes). */
+ * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes); PDEINV_POT_MEANFIELD_MLP,
+ * pdeinv_mf_mlp_supported, pdeinv_mf_mlp_workspace_bytes, pdeinv_mf_mlp_prepare, pdeinv_mf_mlp_force,
+ * pdeinv_mf_mlp_step. */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -76,7 +78,11 @@ typedef enum {
   PDEINV_POT_NONE = 3,
   /* The learned V_hypothesis MLP (core/model.py:32-62), parameters on the device: accepted by
      pdeinv_sde_simulate_mlp only (every other simulator entry point rejects it as an unknown kind). */
-  PDEINV_POT_MLP = 4
+  PDEINV_POT_MLP = 4,
+  /* McKean–Vlasov with the learned interaction Phi_theta = V_hypothesis: grad U(q_i) = mean_j grad Phi_theta(q_i -
+     q_j) over the whole ensemble, update by update: accepted by pdeinv_mf_mlp_step only (every other simulator
+     entry point rejects it as an unknown kind). */
+  PDEINV_POT_MEANFIELD_MLP = 5
 } pdeinv_potential_kind;
 
 typedef struct {
@@ -578,6 +584,41 @@ size_t pdeinv_sde_simulate_mlp_workspace_bytes(const pdeinv_sde_desc* desc, cons
 int pdeinv_sde_simulate_mlp(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape, const float* d_params,
                             const float* d_z0, float* d_traj, float* d_tau, float* d_last, void* d_workspace,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The learned interaction Phi_theta = V_hypothesis of the kinetic McKean–Vlasov system
+ * (methods/consistency_instances/kinetic_mckean_vlasov.py:20-23): the mean-field force and the simulator's update
+ * with it. Tile envelope only (pdeinv_mf_mlp_supported needs no GPU: dim <= 8, width <= 20, 1 <= n_layers <= 8,
+ * any out_features; outside it every entry point returns PDEINV_ERR_UNSUPPORTED before any device call). d_params
+ * as for pdeinv_mlp_potential. Deterministic, no atomics.
+ *
+ * pdeinv_mf_mlp_force — d_force[i*dim + k] = (1/m) sum_{j<m} d_k Phi_theta(x_i - r_j) for items x_i = d_x + i*ldx
+ * (i < n) against references r_j = d_r + j*ldr (ld 0 => dim; < dim: INVALID). The two sets are separate (a rank's
+ * particles against the gathered ensemble); a pair with x_i = r_j counts like any other (x_minus_ref includes the
+ * self pair). x_i - r_j is formed in fp32; partial sums per (item, 256 references by reference index) in fp32, summed
+ * over the chunks in order in fp64. Row i of the result depends on x_i and on the reference set in its order only —
+ * not on n, on the other items of the call or on the launch grid. n == 0 is a no-op; m < 1 is INVALID.
+ *
+ * pdeinv_mf_mlp_prepare — builds the weight image into d_workspace; the steps of one simulate read it.
+ * pdeinv_mf_mlp_step — update s (0..n_steps) of utils/sampling_utils.py:6-22 for the desc's particles: reads
+ * d_z [N, 2d] (row stride desc->ld_z0, the state before the update), takes the force of its position halves against
+ * d_ref [m, ldr] (the positions of the whole ensemble before the update, every rank's), writes d_z_out [N, 2d]
+ * (contiguous) and d_tau_row [N] = tau0 + s*dt (nullable). Streams and clock of pdeinv_mf_step: noise from Philox
+ * with the global id as the counter (d_noise honoured), tau0 shared by the ensemble (d_shift_u must be NULL),
+ * h = tau0 / dt / dt - tau0 for s = 0 / 0 < s < n_steps / s = n_steps. Requires desc->potential.kind ==
+ * PDEINV_POT_MEANFIELD_MLP and desc->dim == shape->dim. The force it applies is pdeinv_mf_mlp_force's bit for bit.
+ * Workspace: pdeinv_mf_mlp_workspace_bytes(shape, n items, m references), 256-byte aligned; the same buffer for
+ * prepare and every step of a simulate.
+ * --------------------------------------------------------------------------------------- */
+int pdeinv_mf_mlp_supported(const pdeinv_mlp_shape* shape);
+size_t pdeinv_mf_mlp_workspace_bytes(const pdeinv_mlp_shape* shape, int64_t n, int64_t m);
+int pdeinv_mf_mlp_prepare(const pdeinv_mlp_shape* shape, const float* d_params, void* d_workspace, void* stream);
+int pdeinv_mf_mlp_force(const pdeinv_mlp_shape* shape, const float* d_params, const float* d_x, int64_t n,
+                        int64_t ldx, const float* d_r, int64_t m, int64_t ldr, float* d_force, void* d_workspace,
+                        void* stream);
+int pdeinv_mf_mlp_step(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape, int32_t s, const float* d_z,
+                       float* d_z_out, float* d_tau_row, const float* d_ref, int64_t m, int64_t ldr,
+                       void* d_workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Exact Gaussian sampler — core/distribution.py:52-65 Gaussian.sample: z = C^{1/2} xi + mu.

@@ -125,6 +125,37 @@ class MLPPotential(Potential):
         return dict(kind=native.POT_MLP, dims=self.dims(), params=self.flat())
 
 
+class MeanFieldMLPPotential(Potential):
+    """McKean–Vlasov with the learned interaction Phi_theta = V_hypothesis (core/model.py:32-62): the drift on
+    particle i is mean_j grad Phi_theta(x_i - x_j) over the whole ensemble (kinetic_mckean_vlasov.py:20-23). `model`
+    a core.model.V_hypothesis, `params` its param tree (device tensors), read live like MLPPotential's. There is no
+    closed-form mean: the simulator runs update by update (utils.mean_field.simulate_mean_field)."""
+
+    def __init__(self, model, params):
+        if getattr(model, "residual_kind", None) != "mlp":
+            raise ValueError("MeanFieldMLPPotential takes a core.model.V_hypothesis")
+        self.model = model
+        self.params = params
+        self.dim = int(params["params"]["layers_0"]["kernel"].shape[0])
+
+    def dims(self):
+        return self.model.dims(self.dim)
+
+    def flat(self) -> torch.Tensor:
+        return self.model.flat(self.params)
+
+    def force(self, x: torch.Tensor, ref: torch.Tensor = None):
+        """F_i = mean_j grad Phi_theta(x_i - ref_j) [n, d]; ref None: the items themselves."""
+        return native.kmv_mlp_force(self.dims(), self.flat(), x, ref)
+
+    def gradient(self, x: torch.Tensor):
+        """The drift of an ensemble x [n, d] on itself (what `resolve` accepts as potential_grad)."""
+        return self.force(x)
+
+    def native_desc(self) -> dict:
+        return dict(kind=native.POT_MEANFIELD_MLP, dims=self.dims(), params=self.flat())
+
+
 def resolve(potential_grad) -> Potential:
     """Accept a Potential or its bound `.gradient` (what the reference passes, …_GMM.py:120)."""
     if isinstance(potential_grad, Potential):

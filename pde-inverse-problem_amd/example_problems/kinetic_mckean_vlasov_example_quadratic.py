@@ -118,18 +118,32 @@ class KineticMcKeanVlasov(KineticFokkerPlanck):
         return 0.5 * torch.sum(x * (x @ F.T), -1)
 
     def simulate_interacting(self, rng: Key, batch_size: int, n_steps: int = None, particle_offset: int = 0,
-                             stamp_sums: bool = False):
+                             stamp_sums: bool = False, interaction=None, n_global: int = None):
         """The McKean–Vlasov particle system (sample_scheme SDE): traj [n, N, 2d], shared tau [n].
+        interaction: None (the problem's own quadratic Phi*) or a core.potential.MeanFieldMLPPotential, a learned
+        Phi_theta — simulated update by update against the whole ensemble of n_global particles (default: the
+        all-reduced batch sizes); it has no stamp sums (stamp_sums=True raises ValueError).
         stamp_sums=True: no trajectory; instead the quadratic-Phi KMV residual's per-stamp sums formed inside the
         simulator ("kmv_mom" / "kmv_wst", pdeinv_sde_simulate_mf_kmv) and the shared stamps "tau_0T" [n] (fp64 of
         the simulator's fp32 stamps, computed on the host from the same Philox draw)."""
+        from core.potential import MeanFieldMLPPotential
         from utils.mean_field import simulate_mean_field, stamp_times
+        learned = isinstance(interaction, MeanFieldMLPPotential)
+        if interaction is not None and not learned:
+            raise TypeError("simulate_interacting: interaction must be None or a MeanFieldMLPPotential")
+        if learned and stamp_sums:
+            raise ValueError("simulate_interacting: stamp_sums are the quadratic-Phi KMV sums of the fused simulator; "
+                             "a learned interaction returns its trajectory instead")
         n_steps = n_steps or self.n_steps
         k_init, k_sde = prng.split(rng)
         z0 = self.distribution_initial.sample(batch_size, k_init, row_offset=particle_offset)
         dt = self.total_evolving_time / n_steps
         gamma = self.initial_configuration["gamma_friction"]
         ctr = self._next_counter(n_steps)
+        if learned:
+            r = simulate_mean_field(z0, n_steps, dt, k_sde, interaction, gamma, particle_offset=particle_offset,
+                                    counter_offset=ctr, n_global=n_global)
+            return z0, r
         if not stamp_sums:
             r = simulate_mean_field(z0, n_steps, dt, k_sde, self.interaction, gamma, particle_offset=particle_offset,
                                     counter_offset=ctr)

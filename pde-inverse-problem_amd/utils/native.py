@@ -28,6 +28,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "_build", "libpdeinv.so")
 PDEINV_OK, PDEINV_ERR_INVALID, PDEINV_ERR_UNSUPPORTED, PDEINV_ERR_HIP = 0, -1, -2, -3
 POT_QUADRATIC, POT_GMM, POT_MEANFIELD_QUADRATIC, POT_NONE = 0, 1, 2, 3
 POT_MLP = 4  # the learned V_hypothesis: sde_simulate_mlp only
+POT_MEANFIELD_MLP = 5  # the learned interaction Phi_theta: mf_mlp_step only
 MAX_DIM, MAX_PARAMS = 16, 256
 KFP_NOUT = 9
 KFP_SLOTS = ("loss", "loss ground truth", "grad_norm", "loss_nabla", "loss_Hessian",
@@ -66,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "pdeinv_kmv_weights_from_ds_workspace_bytes", "pdeinv_kmv_weights_from_ds",
     "pdeinv_mlp_potential_path", "pdeinv_mlp_potential_workspace_bytes", "pdeinv_mlp_potential",
     "pdeinv_sde_simulate_mlp_supported", "pdeinv_sde_simulate_mlp_workspace_bytes", "pdeinv_sde_simulate_mlp",
+    "pdeinv_mf_mlp_supported", "pdeinv_mf_mlp_workspace_bytes", "pdeinv_mf_mlp_prepare", "pdeinv_mf_mlp_force",
+    "pdeinv_mf_mlp_step",
 )
 
 
@@ -235,6 +238,11 @@ def lib():
         "pdeinv_sde_simulate_mlp_supported": (ctypes.c_int, [P]),
         "pdeinv_sde_simulate_mlp_workspace_bytes": (ctypes.c_size_t, [P, P]),
         "pdeinv_sde_simulate_mlp": (i32, [P, P, P, P, P, P, P, P, P]),
+        "pdeinv_mf_mlp_supported": (ctypes.c_int, [P]),
+        "pdeinv_mf_mlp_workspace_bytes": (ctypes.c_size_t, [P, i64, i64]),
+        "pdeinv_mf_mlp_prepare": (i32, [P, P, P, P]),
+        "pdeinv_mf_mlp_force": (i32, [P, P, P, i64, i64, P, i64, i64, P, P, P]),
+        "pdeinv_mf_mlp_step": (i32, [P, P, i32, P, P, P, P, i64, i64, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -481,6 +489,88 @@ def sde_simulate_mlp(z0: torch.Tensor, n_steps: int, dt: float, gamma: float, di
     del p_host
     _check(rc, "pdeinv_sde_simulate_mlp")
     return res
+
+
+# -----------------------------------------------------------------------------------------
+# McKean–Vlasov with the learned interaction Phi_theta = V_hypothesis
+# -----------------------------------------------------------------------------------------
+def mf_mlp_supported(dims) -> bool:
+    """The tile envelope of the learned-interaction kernels (dim <= 8, width <= 20, 1..8 layers). Needs no GPU."""
+    return bool(lib().pdeinv_mf_mlp_supported(ctypes.byref(mlp_shape(dims))))
+
+
+def _mf_mlp_ws(shape: MlpShape, n: int, m: int, device) -> Optional[torch.Tensor]:
+    """The workspace, or None outside the envelope (the native call then reports it; nothing is launched)."""
+    if not lib().pdeinv_mf_mlp_supported(ctypes.byref(shape)):
+        return None
+    nbytes = lib().pdeinv_mf_mlp_workspace_bytes(ctypes.byref(shape), int(n), int(m))
+    return torch.empty(max(nbytes // 4, 64), device=device, dtype=torch.float32)
+
+
+def kmv_mlp_force(dims, params_flat: torch.Tensor, x: torch.Tensor, ref: Optional[torch.Tensor] = None):
+    """The mean-field force of the learned interaction, F_i = mean_j grad Phi_theta(x_i - ref_j) [n, d]
+    (pdeinv_mf_mlp_force; kinetic_mckean_vlasov.py:20-23, the self pair included). x [n, d] items, ref [m, d]
+    references (None: the items themselves); rows of either may be strided views (unit inner stride).
+    params_flat: the device flat flax vector, read on the current stream."""
+    _require_gpu()
+    shape = mlp_shape(dims)
+    d = shape.dim
+    pp = _mlp_params(shape, params_flat)
+    ref = x if ref is None else ref
+    n, m = x.shape[0], ref.shape[0]
+    xp, _, ldx = _rows(x, "x", d) if n > 0 else (None, 0, d)
+    rp, _, ldr = _rows(ref, "ref", d) if m > 0 else (None, 0, d)
+    f = torch.empty((n, d), device=x.device, dtype=torch.float32)
+    ws = _mf_mlp_ws(shape, n, max(m, 1), x.device)
+    _check(lib().pdeinv_mf_mlp_force(ctypes.byref(shape), pp, xp, n, ldx, rp, m, ldr, _dev(f, "force"),
+                                     _dev(ws, "workspace"), stream_handle()), "pdeinv_mf_mlp_force")
+    return f
+
+
+def mf_mlp_desc(N: int, d: int, n_steps: int, dt: float, gamma: float, *, seed: int, counter_offset: int = 0,
+                particle_offset: int = 0, noise_scale: float = SQRT2, random_shift: bool = True,
+                noise: Optional[torch.Tensor] = None) -> SdeDesc:
+    """mf_desc for the learned interaction (potential kind POT_MEANFIELD_MLP; no host parameters)."""
+    desc, _ = mf_desc(N, d, n_steps, dt, gamma, None, seed=seed, counter_offset=counter_offset,
+                      particle_offset=particle_offset, noise_scale=noise_scale, random_shift=random_shift, noise=noise)
+    desc.potential = PotentialDesc(POT_MEANFIELD_MLP, 0, 1.0, 0, None)
+    return desc
+
+
+def mf_mlp_prepare(dims, params_flat: torch.Tensor, n: int, m: int) -> torch.Tensor:
+    """The workspace of one simulate of n local particles against m ensemble positions, with the weight image
+    of params_flat built into it (pdeinv_mf_mlp_prepare): pass it to every mf_mlp_step of the simulate."""
+    _require_gpu()
+    shape = mlp_shape(dims)
+    pp = _mlp_params(shape, params_flat)
+    ws = _mf_mlp_ws(shape, n, m, params_flat.device)
+    _check(lib().pdeinv_mf_mlp_prepare(ctypes.byref(shape), pp, _dev(ws, "workspace"), stream_handle()),
+           "pdeinv_mf_mlp_prepare")
+    return ws
+
+
+def mf_mlp_step(desc: SdeDesc, dims, s: int, z: torch.Tensor, z_out: torch.Tensor, tau_row, ref: torch.Tensor,
+                ws: torch.Tensor) -> None:
+    """Update s of the desc's particles (pdeinv_mf_mlp_step): z [N, 2d] (unit inner stride) -> z_out [N, 2d]
+    (contiguous), the force taken against ref [m, d], the positions of the whole ensemble before the update."""
+    shape = mlp_shape(dims)
+    N, d = desc.n_particles, desc.dim
+    if tuple(z.shape) != (N, 2 * d) or (N and z.stride(1) != 1):
+        raise ValueError(f"z must be [{N}, {2 * d}] with unit inner stride")
+    if tuple(z_out.shape) != (N, 2 * d) or not z_out.is_contiguous():
+        raise ValueError(f"z_out must be contiguous [{N}, {2 * d}]")
+    if tau_row is not None and (tuple(tau_row.shape) != (N,) or not tau_row.is_contiguous()):
+        raise ValueError(f"tau_row must be contiguous [{N}]")
+    rp, m, ldr = _rows(ref, "ref", d)
+    need = lib().pdeinv_mf_mlp_workspace_bytes(ctypes.byref(shape), N, max(m, 1))
+    if ws is not None and ws.numel() * ws.element_size() < need:
+        raise ValueError(f"workspace of {ws.numel() * ws.element_size()} bytes, {need} needed for {N} particles "
+                         f"against {m} references (mf_mlp_prepare with these counts)")
+    desc.ld_z0 = z.stride(0) if N > 1 else 2 * d
+    rc = lib().pdeinv_mf_mlp_step(ctypes.byref(desc), ctypes.byref(shape), int(s), _dev(z, "z") if N else None,
+                                  _dev(z_out, "z_out") if N else None, _dev(tau_row, "tau_row"), rp, m, ldr,
+                                  _dev(ws, "workspace"), stream_handle())
+    _check(rc, "pdeinv_mf_mlp_step")
 
 
 def sde_tau0(N: int, dt: float, *, seed: int, counter_offset: int = 0, particle_offset: int = 0,

@@ -16,7 +16,7 @@ from typing import Optional
 
 import torch
 
-from core.potential import MeanFieldQuadraticPotential, MLPPotential, resolve
+from core.potential import MeanFieldMLPPotential, MeanFieldQuadraticPotential, MLPPotential, resolve
 from utils import native
 from utils.prng import Key
 
@@ -30,7 +30,7 @@ def simulate(q0_p0: torch.Tensor, n_steps: int, dt: float, key: Key, potential_g
              last: bool = True, moments: bool = False, out: Optional[dict] = None) -> dict:
     """Time-major simulator call. Returns dict(traj [n,N,2d], tau [n,N], last [N,2d], moments [3,L])."""
     pot = resolve(potential_grad)
-    if isinstance(pot, MeanFieldQuadraticPotential):
+    if isinstance(pot, (MeanFieldQuadraticPotential, MeanFieldMLPPotential)):  # the learned one: per-update driver
         from utils.mean_field import simulate_mean_field
         return simulate_mean_field(q0_p0, n_steps, dt, key, pot, gamma_friction, particle_offset=particle_offset,
                                    counter_offset=counter_offset, noise_scale=noise_scale,
