@@ -5,7 +5,8 @@
 // file does not cover): for methods/consistency_instances/kinetic_mckean_vlasov.py:11-120 with a
 // non-parametric Phi_theta = V_hypothesis (core/model.py:32-62: tanh layers, Dense(40), sum of
 // squares), every pair (i, j) of a time stamp's particles, y_ij = x_i - x_j (x_minus_ref, :20-23),
-// contributes grad Phi(y_ij) (pass 1: gbar_i = mean_j grad Phi), and pass 2 differentiates
+// contributes grad Phi(y_ij) (pass 1: gbar_i = mean_j grad Phi — the pair force below, which is also the
+// learned interaction of sde_mf_mlp.hip, with x = r = z per time stamp), and pass 2 differentiates
 //     l_ij = u_i . grad Phi(y_ij) + c2 v_i^T Hess Phi(y_ij) v_i + c0_i Phi(y_ij)
 // (u_i = 2 s gbar_i, c2 = -2 s, c0_i = 2 s w_it; s = 1 / (n^2 n_sets); loss assembly :74-97) with
 // respect to theta. Covered: dim <= 8, width <= 20 (zero-padded to 20), 1 <= n_layers <= 8, any
@@ -34,6 +35,14 @@
 // Weights: one image per call (kmvq_image_kernel), lane-linear A-operand fragments of every product
 // (forward: K^T with rows = outputs; backward: K with rows = inputs), staged once per persistent block
 // into LDS and read as 16-B fragments.
+//
+// Pair force (pair_force_kernel, declared in mlp_tile.h). A wave owns one (item, chunk of kChunk references
+// by reference index) unit, walks the chunk in 16-pair tiles — y = x_i - r_j formed in fp32 — and runs
+// mlpq::tile_grad on each. The tile gradients of a lane add up in registers in tile order, the 16 lanes of a
+// coordinate fold in a fixed butterfly, and the unit's D sums go to gpart[item][chunk]. No atomics. Tail
+// tiles and the short last chunk load from a clamped row (load_ref); their pairs run the tile at y = 0 and
+// are dropped by a select. The chunk partials of an item are summed in chunk order in fp64 and scaled by a
+// double 1/m (reduce_chunks), by pair_force_reduce_kernel or at the head of sde_mf_mlp.hip's update.
 #include <math.h>
 #include <stdlib.h>
 
@@ -45,30 +54,24 @@
 namespace pdeinv {
 namespace mlpq {
 
-constexpr int kWaves = 8;   // waves per block of pass 1 (two blocks per CU)
+constexpr int kWaves = 8;   // waves per block of the pair force (two blocks per CU = 4 waves per SIMD)
 constexpr int kWaves2 = 4;   // waves per block of pass 2: one per SIMD (512 registers: the checkpoints stay in registers)
-constexpr int kChunk = 256;  // references per work unit (16 tiles)
-constexpr int kPS = 28;      // LDS image row pitch (floats); odd rows shifted by one 16-byte chunk (img_at)
+constexpr int kPS = 28;     // LDS image row pitch (floats); odd rows shifted by one 16-byte chunk (img_at)
 constexpr int kRowsA = 48, kRowsB = 32;
 constexpr int kTImg = (kRowsA + kRowsB) * kPS;  // floats per wave: the [A | B] transpose images
 
-struct Args {
-  int L, D, n_ch;
-  int64_t n, n_items, n_units, set_stride, ld;
+struct Args {  // pass 2
+  int n_ch;
+  int64_t n, n_units, set_stride, ld;
   const float* z;
   const float* ds;
-  float gamma, s, inv_n;
-  const float* img;       // weight image (device), img_floats (multiple of 4)
-  int img_floats;
-  int fwd[kLMax + 1], bwd[kLMax + 1], bias[kLMax + 1];  // unit offsets (fwd / bwd), float offsets (bias)
-  int qoff[kLMax + 1];                                  // gradient-slab offsets (padded layout)
-  int fwd_out, bias_out, qoff_out;                      // the output layer's (index L: scalar kernel args)
-  int h0_off;                                           // h0 = the last hidden layer at input 0 (float offset)
-  int P;                                                // padded parameter count
-  const float* gbar;      // pass 2: [n_items][D]
-  float* gpart;           // pass 1: [n_units][D]
-  float* gslab;           // pass 2: [n_blocks][P]
-  float* aslab;           // pass 2: [n_waves][8]
+  float gamma, s;
+  TileNet net;
+  int qoff[kLMax + 1], qoff_out;  // gradient-slab offsets (padded layout); the output layer's
+  int P;                          // padded parameter count
+  const float* gbar;      // [n_items][D]
+  float* gslab;           // [n_blocks][P]
+  float* aslab;           // [n_waves][8]
 };
 
 // v_mfma_f32_4x4x1_16b_f32: 16 independent 4 x 4 outer products; lane 4b + j, register i of the result
@@ -250,18 +253,18 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
   const int slab_f = (a.P + 3) & ~3;
   const int lane0 = threadIdx.x & (kWave - 1), p = lane0 & 15, g = lane0 >> 4;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  float* slab = lds + a.img_floats + wib * slab_f;  // this wave's private gradient slab
-  float* tA0 = lds + a.img_floats + kWaves2 * slab_f + wib * kTImg;
+  float* slab = lds + a.net.img_floats + wib * slab_f;  // this wave's private gradient slab
+  float* tA0 = lds + a.net.img_floats + kWaves2 * slab_f + wib * kTImg;
   float* tB0 = tA0 + kRowsA * kPS;
   float* tA1 = tA0;
   float* tB1 = tB0;
-  for (int q = threadIdx.x; q < a.img_floats / 4; q += blockDim.x) lds4[q] = reinterpret_cast<const f32x4*>(a.img)[q];
-  for (int q = threadIdx.x; q < kWaves2 * (slab_f + kTImg); q += blockDim.x) lds[a.img_floats + q] = 0.f;
+  stage_image(lds4, a.net);
+  for (int q = threadIdx.x; q < kWaves2 * (slab_f + kTImg); q += blockDim.x) lds[a.net.img_floats + q] = 0.f;
   __syncthreads();
 
   const int64_t wave = (int64_t)blockIdx.x * kWaves2 + wib;
   const int64_t n_waves = (int64_t)gridDim.x * kWaves2;
-  const int L = a.L, D = a.D;
+  const int L = a.net.L, D = a.net.D;
   const float c2 = -2.f * a.s;
   float accs[3] = {0.f, 0.f, 0.f};  // LOSS, HESSIAN, FRICTION slot partials
   float cs[kNS] = {}, c0sum = 0.f;   // sum c0 h (the dl/dc remainder), sum c0 (dl/db's |b|^2 term)
@@ -282,7 +285,7 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
 
     // layer-0 tangents along u and v: the same for every pair of the item
     float w0[4];
-    load_units<4>(img, a.fwd[0], lane0, w0);  // unit kk * 2 + mb
+    load_units<4>(img, a.net.fwd[0], lane0, w0);  // unit kk * 2 + mb
     float zu0[kNS], zv0[kNS], zw0[kNS];
     {
       f32x4 Au[2] = {}, Av[2] = {};
@@ -300,15 +303,7 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
     }
 
     float xn[KD];  // next tile's reference coordinates (prefetched)
-    {
-      const int64_t j = ch * kChunk + p;
-#pragma unroll
-      for (int kk = 0; kk < KD; ++kk) {
-        const int k = 4 * kk + g;
-        const float v = zt[(j < j_end ? j : j_end - 1) * a.ld + (k < D ? k : D - 1)];  // unconditional load
-        xn[kk] = (j < j_end && k < D) ? v : 0.f;
-      }
-    }
+    load_ref<KD>(zt, a.ld, D, g, ch * kChunk + p, j_end, xn);
     for (int64_t j0 = ch * kChunk; j0 < j_end; j0 += 16) {
       // the weight fragments are the same for every tile: an opaque lane index keeps the compiler from
       // hoisting all of them out of the tile loop (hundreds of VGPRs)
@@ -321,21 +316,13 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
       float yb[KD];
 #pragma unroll
       for (int kk = 0; kk < KD; ++kk) yb[kk] = (active && 4 * kk + gq < D) ? xi[kk] - xn[kk] : 0.f;
-      {
-        const int64_t j = j0 + 16 + p;
-#pragma unroll
-        for (int kk = 0; kk < KD; ++kk) {
-          const int k = 4 * kk + gq;
-          const float v = zt[(j < j_end ? j : j_end - 1) * a.ld + (k < D ? k : D - 1)];  // unconditional load
-        xn[kk] = (j < j_end && k < D) ? v : 0.f;
-        }
-      }
+      load_ref<KD>(zt, a.ld, D, gq, j0 + 16 + p, j_end, xn);  // under this tile's products
       // ---- forward ----
       float ckh[kLMax][kNS], cku[kLMax][kNS], ckv[kLMax][kNS], ckw[kLMax][kNS];
       float H[4][kNS];
       {
         f32x4 A[2];
-        bias_hidden(img, a.bias[0], gq, A);
+        bias_hidden(img, a.net.bias[0], gq, A);
 #pragma unroll
         for (int kk = 0; kk < KD; ++kk)
 #pragma unroll
@@ -350,9 +337,9 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
       for (int l = 1; l < kLMax; ++l) {
         if (l < L) {
           float w[12];
-          load_units<12>(img, a.fwd[l], lane, w);  // unit kk * 2 + mb
+          load_units<12>(img, a.net.fwd[l], lane, w);  // unit kk * 2 + mb
           f32x4 A[4][2] = {};
-          bias_hidden(img, a.bias[l], gq, A[0]);
+          bias_hidden(img, a.net.bias[l], gq, A[0]);
 #pragma unroll
           for (int s = 0; s < 4; ++s)  // stream-major: the primal's tanh overlaps the tangents' MFMAs
 #pragma unroll
@@ -383,12 +370,12 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
         // dh = h - h0, y0 = K_L^T h0 + b, c0 = K_L y0): every term is then O(|y|) where the net's output
         // y is small — pairs near the origin of a trained net, where Phi*(0) = 0 — instead of the
         // difference of O(|b|^2) terms (the unshifted fold's fp32 cancellation)
-        const float* h0p = img + a.h0_off;
+        const float* h0p = img + a.net.h0_off;
 #pragma unroll
         for (int k = 0; k < 4; ++k) H[0][k] -= h0p[4 * gq + k];
         H[0][4] -= h0p[16 + gq];
         float w[12];
-        load_units<12>(img, a.fwd_out, lane, w);  // M, unit kk * 2 + mb
+        load_units<12>(img, a.net.fwd_out, lane, w);  // M, unit kk * 2 + mb
         f32x4 Mh[4][2] = {};
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -399,7 +386,7 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
         float m[4][kNS], cv[kNS];
 #pragma unroll
         for (int s = 0; s < 4; ++s) compact_hidden(Mh[s], m[s]);
-        const float* cb = img + a.bias_out;  // c0[20], |y0|^2
+        const float* cb = img + a.net.bias_out;  // c0[20], |y0|^2
 #pragma unroll
         for (int k = 0; k < 4; ++k) cv[k] = cb[4 * gq + k];
         cv[4] = cb[16 + gq];
@@ -458,7 +445,7 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
           const float(&pv)[kNS] = l - 1 == 0 ? zv0 : ckv[l - 1];
           const float(&pw)[kNS] = l - 1 == 0 ? zw0 : ckw[l - 1];
           float w[12];
-          load_units<12>(img, a.bwd[l], lane, w);  // unit kk * 2 + mb
+          load_units<12>(img, a.net.bwd[l], lane, w);  // unit kk * 2 + mb
           f32x4 G0 = {}, E = {}, B[4][2] = {};
           const EdgeMap em(lane);
           auto step = [&](auto sc) {
@@ -551,140 +538,46 @@ __global__ __launch_bounds__(kWaves2 * kWave, 1) void kmvq_grad_kernel(Args a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// pass 1: gbar partials per (item, chunk of references): sum_j grad_y Phi(x_i - x_j)
+// pair force: the partials per (item, chunk of references), sum_j grad_y Phi(x_i - r_j), and their reduce
 // -------------------------------------------------------------------------------------------------
 template <int KD>
-__global__ __launch_bounds__(kWaves * kWave, 2) void kmvq_gbar_kernel(Args a) {
+__global__ __launch_bounds__(kWaves * kWave, 2) void pair_force_kernel(PairForce a) {
   extern __shared__ f32x4 lds4[];
   float* img = reinterpret_cast<float*>(lds4);
-  for (int q = threadIdx.x; q < a.img_floats / 4; q += blockDim.x) lds4[q] = reinterpret_cast<const f32x4*>(a.img)[q];
+  stage_image(lds4, a.net);
   __syncthreads();
   const int lane0 = threadIdx.x & (kWave - 1), p = lane0 & 15, g = lane0 >> 4;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int64_t wave = (int64_t)blockIdx.x * kWaves + wib;
   const int64_t n_waves = (int64_t)gridDim.x * kWaves;
-  const int L = a.L, D = a.D;
-  for (int64_t unit = wave; unit < a.n_units; unit += n_waves) {
-    const int64_t it = unit / a.n_ch, ch = unit - it * a.n_ch;
+  const int D = a.net.D;
+  const int64_t n_ch = pair_chunks(a.m), n_units = a.n_sets * a.n * n_ch;
+  for (int64_t unit = wave; unit < n_units; unit += n_waves) {
+    const int64_t it = unit / n_ch, ch = unit - it * n_ch;
     const int64_t t = it / a.n, i = it - t * a.n;
-    const int64_t j_end = (ch + 1) * kChunk < a.n ? (ch + 1) * kChunk : a.n;
-    const float* zt = a.z + t * a.set_stride;
+    const int64_t j_end = (ch + 1) * kChunk < a.m ? (ch + 1) * kChunk : a.m;
+    const float* rt = a.r + t * a.r_set;
     float xi[KD];
-    lane_dims<KD>(zt + i * a.ld, D, g, xi);
-    float w0[4];
-    load_units<4>(img, a.fwd[0], lane0, w0);
+    lane_dims<KD>(a.x + t * a.x_set + i * a.ldx, D, g, xi);
     f32x4 gacc = {};
     float xn[KD];
-    {
-      const int64_t j = ch * kChunk + p;
-#pragma unroll
-      for (int kk = 0; kk < KD; ++kk) {
-        const int k = 4 * kk + g;
-        const float v = zt[(j < j_end ? j : j_end - 1) * a.ld + (k < D ? k : D - 1)];  // unconditional load
-        xn[kk] = (j < j_end && k < D) ? v : 0.f;
-      }
-    }
+    load_ref<KD>(rt, a.ldr, D, g, ch * kChunk + p, j_end, xn);
     for (int64_t j0 = ch * kChunk; j0 < j_end; j0 += 16) {
-      // the weight fragments are the same for every tile: an opaque lane index keeps the compiler from
-      // hoisting all of them out of the tile loop (hundreds of VGPRs)
+      // the weight fragments are the same for every tile: an opaque lane index keeps the compiler from hoisting
+      // all of them out of the tile loop (hundreds of VGPRs)
       int lane = lane0;
       asm volatile("" : "+v"(lane));
-      const int gq = lane >> 4;  // (opaque too: the bias reads)
       const bool active = j0 + p < j_end;
       float yb[KD];
 #pragma unroll
       for (int kk = 0; kk < KD; ++kk) yb[kk] = (active && 4 * kk + g < D) ? xi[kk] - xn[kk] : 0.f;
-      {
-        const int64_t j = j0 + 16 + p;
+      load_ref<KD>(rt, a.ldr, D, g, j0 + 16 + p, j_end, xn);  // the next tile's rows, under this tile's products
+      float unused;
+      const f32x4 ga = tile_grad<KD, false>(img, a.net, lane, yb, unused);
 #pragma unroll
-        for (int kk = 0; kk < KD; ++kk) {
-          const int k = 4 * kk + g;
-          const float v = zt[(j < j_end ? j : j_end - 1) * a.ld + (k < D ? k : D - 1)];  // unconditional load
-        xn[kk] = (j < j_end && k < D) ? v : 0.f;
-        }
-      }
-      float ckh[kLMax][kNS];
-      {
-        f32x4 A[2];
-        bias_hidden(img, a.bias[0], gq, A);
-#pragma unroll
-        for (int kk = 0; kk < KD; ++kk)
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb) A[mb] = mfma(w0[kk * 2 + mb], yb[kk], A[mb]);
-        float z[kNS];
-        compact_hidden(A, z);
-#pragma unroll
-        for (int k = 0; k < kNS; ++k) ckh[0][k] = ftanh(z[k]);
-      }
-      float h[kNS];
-#pragma unroll
-      for (int k = 0; k < kNS; ++k) h[k] = ckh[0][k];
-#pragma unroll
-      for (int l = 1; l < kLMax; ++l) {
-        if (l < L) {
-          float w[12];
-          load_units<12>(img, a.fwd[l], lane, w);
-          f32x4 A[2];
-          bias_hidden(img, a.bias[l], gq, A);
-#pragma unroll
-          for (int kk = 0; kk < kNS; ++kk)
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) A[mb] = mfma(w[kk * 2 + mb], h[kk], A[mb]);
-          float z[kNS];
-          compact_hidden(A, z);
-#pragma unroll
-          for (int k = 0; k < kNS; ++k) h[k] = ckh[l][k] = ftanh(z[k]);
-        }
-      }
-      float hb[kNS];
-      {  // dPhi/dh = 2 (M (h - h0) + c0): the output layer as a quadratic form (see the gradient kernel)
-        const float* h0p = img + a.h0_off;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) h[k] -= h0p[4 * gq + k];
-        h[4] -= h0p[16 + gq];
-        float w[12];
-        load_units<12>(img, a.fwd_out, lane, w);
-        f32x4 Mh[2] = {};
-#pragma unroll
-        for (int kk = 0; kk < kNS; ++kk)
-#pragma unroll
-          for (int mb = 0; mb < 2; ++mb) Mh[mb] = mfma(w[kk * 2 + mb], h[kk], Mh[mb]);
-        float m[kNS];
-        compact_hidden(Mh, m);
-        const float* cb = img + a.bias_out;
-#pragma unroll
-        for (int k = 0; k < kNS; ++k) {
-          const float c = k < 4 ? cb[4 * gq + k] : cb[16 + gq];
-          hb[k] = active ? 2.f * (m[k] + c) : 0.f;
-        }
-      }
-#pragma unroll
-      for (int l = kLMax - 1; l >= 1; --l) {
-        if (l < L) {
-          float zb[kNS];
-#pragma unroll
-          for (int k = 0; k < kNS; ++k) zb[k] = (1.f - ckh[l][k] * ckh[l][k]) * hb[k];
-          float w[12];
-          load_units<12>(img, a.bwd[l], lane, w);
-          f32x4 B[2] = {};
-#pragma unroll
-          for (int kk = 0; kk < kNS; ++kk)
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) B[mb] = mfma(w[kk * 2 + mb], zb[kk], B[mb]);
-          compact_hidden(B, hb);
-        }
-      }
-      {
-        float zb[kNS];
-#pragma unroll
-        for (int k = 0; k < kNS; ++k) zb[k] = (1.f - ckh[0][k] * ckh[0][k]) * hb[k];
-        float w[8];
-        load_units<8>(img, a.bwd[0], lane, w);  // unit kk (one M block: rows = input dims)
-#pragma unroll
-        for (int kk = 0; kk < kNS; ++kk) gacc = mfma(w[kk], zb[kk], gacc);
-      }
+      for (int r = 0; r < 4; ++r) gacc[r] += active ? ga[r] : 0.f;
     }
-    // sum over the 16 pairs of the lane row, dims 4 g + r
+    // sum over the 16 pairs of the lane row, coordinates 4 g + r
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float v = gacc[r];
@@ -696,16 +589,13 @@ __global__ __launch_bounds__(kWaves * kWave, 2) void kmvq_gbar_kernel(Args a) {
   }
 }
 
-// gbar[it][k] = inv_n sum_ch gpart[it][ch][k] (fixed order, fp64)
-__global__ void kmvq_gbar_reduce_kernel(const float* __restrict__ gpart, int64_t n_items, int n_ch, int D, float inv_n,
-                                        float* __restrict__ gbar) {
-  const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(kBlock) void pair_force_reduce_kernel(const float* __restrict__ gpart, int64_t n_items,
+                                                                   int n_ch, int D, double inv_m,
+                                                                   float* __restrict__ out) {
+  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (q >= n_items * D) return;
   const int64_t it = q / D;
-  const int k = (int)(q - it * D);
-  double s = 0.0;
-  for (int c = 0; c < n_ch; ++c) s += (double)gpart[(it * n_ch + c) * D + k];
-  gbar[q] = (float)(s * inv_n);
+  out[q] = reduce_chunks(gpart, it, n_ch, D, (int)(q - it * D), inv_m);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -877,39 +767,58 @@ int build_image(const ImageArgs& ia, const float* params, double* h0y0, float* i
   return check_launch("kmvq_image_kernel");
 }
 
-}  // namespace mlpq
-
-// ---- host driver ------------------------------------------------------------------------------
-namespace {
-
 int device_cus() {
   int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                              hipSuccess || cus <= 0)
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
     cus = 256;
   return cus;
 }
 
+int pair_force_partials(const PairForce& f, hipStream_t st) {
+  const int64_t n_units = f.n_sets * f.n * pair_chunks(f.m);
+  if (n_units <= 0) return PDEINV_OK;
+  const int64_t need = (n_units + kWaves - 1) / kWaves, cap = 2 * (int64_t)device_cus();
+  const dim3 gr((unsigned)(need < cap ? need : cap)), bl(kWaves * kWave);
+  const size_t lds = sizeof(float) * (size_t)f.net.img_floats;
+  if (f.net.D <= 4) {
+    allow_lds(pair_force_kernel<1>);
+    hipLaunchKernelGGL(pair_force_kernel<1>, gr, bl, lds, st, f);
+  } else {
+    allow_lds(pair_force_kernel<2>);
+    hipLaunchKernelGGL(pair_force_kernel<2>, gr, bl, lds, st, f);
+  }
+  return check_launch("pair_force_kernel");
+}
+
+int pair_force_reduce(const float* gpart, int64_t n_items, int n_ch, int D, double inv_m, float* out,
+                      hipStream_t st) {
+  const int64_t nq = n_items * D;
+  if (nq <= 0) return PDEINV_OK;
+  hipLaunchKernelGGL(pair_force_reduce_kernel, dim3((unsigned)((nq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                     gpart, n_items, n_ch, D, inv_m, out);
+  return check_launch("pair_force_reduce_kernel");
+}
+
+}  // namespace mlpq
+
+// ---- host driver of the residual ---------------------------------------------------------------
+namespace {
+
 struct QPlan {
-  mlpq::ImageArgs ia;
+  mlpq::ImagePlan ip;
   MlpPadMap pm;
-  int KD, n_ch, n_blocks2, n_blocks1;
+  int n_ch, n_blocks2;
   int64_t items, n_units, P;
-  int fwd[mlpq::kLMax + 1], bwd[mlpq::kLMax + 1];
-  size_t lds2, lds1;                                                    // bytes
+  size_t lds2;                                                               // bytes
   size_t off_img, off_gbar, off_gpart, off_gslab, off_aslab, off_h0, total;  // bytes
 };
 
 QPlan q_plan(const pdeinv_kmv_mlp_desc* d) {
   QPlan p{};
   const int L = d->n_layers;
-  {
-    const mlpq::ImagePlan ip = mlpq::image_plan(d->dim, L, d->width, d->out_features);
-    p.ia = ip.ia;
-    p.KD = ip.KD;
-    for (int l = 0; l <= L; ++l) { p.fwd[l] = ip.fwd[l]; p.bwd[l] = ip.bwd[l]; }
-  }
-  mlpq::ImageArgs& ia = p.ia;
+  p.ip = mlpq::image_plan(d->dim, L, d->width, d->out_features);
+  const mlpq::ImageArgs& ia = p.ip.ia;
   // padded parameter layout of the gradient slab: K [pin][20] then b [20] for the tanh layers (row
   // pitch 20: 4 pitch = 16 mod 32), then the folded output layer's region (kOutRegion floats). The
   // pad map covers the tanh layers only (pm.L = L - 1); the output region goes through kmvq_out_post_kernel.
@@ -933,41 +842,26 @@ QPlan q_plan(const pdeinv_kmv_mlp_desc* d) {
   }
   p.P = po;
   p.items = (int64_t)d->n_sets * d->n_rows;
-  p.n_ch = (int)((d->n_rows + mlpq::kChunk - 1) / mlpq::kChunk);
+  p.n_ch = mlpq::pair_chunks(d->n_rows);
   p.n_units = p.items * p.n_ch;
-  const int cus = device_cus();
-  const int64_t need1 = (p.n_units + mlpq::kWaves - 1) / mlpq::kWaves;
+  const int cus = mlpq::device_cus();
   const int64_t need2 = (p.n_units + mlpq::kWaves2 - 1) / mlpq::kWaves2;
   p.n_blocks2 = (int)(need2 < cus ? need2 : cus);
-  p.n_blocks1 = (int)(need1 < 2 * cus ? need1 : 2 * cus);
-  p.lds1 = sizeof(float) * (size_t)ia.img_floats;
   p.lds2 = sizeof(float) * ((size_t)ia.img_floats +
                             (size_t)mlpq::kWaves2 * ((((size_t)p.P + 3) & ~(size_t)3) + mlpq::kTImg));
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-  p.off_img = take(sizeof(float) * (size_t)ia.img_floats);
-  p.off_gbar = take(sizeof(float) * (size_t)p.items * d->dim);
-  p.off_gpart = take(sizeof(float) * (size_t)p.n_units * d->dim);
-  p.off_gslab = take(sizeof(float) * (size_t)cus * mlpq::kWaves2 * p.P);
-  p.off_aslab = take(sizeof(float) * (size_t)cus * mlpq::kWaves2 * 8);
-  p.off_h0 = take(sizeof(double) * (size_t)(d->width + d->out_features));
-  p.total = o;
+  using mlpq::take;
+  p.off_img = take(p.total, sizeof(float) * (size_t)ia.img_floats);
+  p.off_gbar = take(p.total, sizeof(float) * (size_t)p.items * d->dim);
+  p.off_gpart = take(p.total, sizeof(float) * (size_t)p.n_units * d->dim);
+  p.off_gslab = take(p.total, sizeof(float) * (size_t)cus * mlpq::kWaves2 * p.P);
+  p.off_aslab = take(p.total, sizeof(float) * (size_t)cus * mlpq::kWaves2 * 8);
+  p.off_h0 = take(p.total, sizeof(double) * (size_t)(d->width + d->out_features));
   return p;
 }
 
 template <int KD>
-int q_launch(const mlpq::Args& a, const QPlan& p, hipStream_t st, int pass) {
-  if (pass == 0) {
-    static const bool attr = hipFuncSetAttribute((const void*)mlpq::kmvq_gbar_kernel<KD>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-    (void)attr;
-    hipLaunchKernelGGL((mlpq::kmvq_gbar_kernel<KD>), dim3((unsigned)p.n_blocks1), dim3(mlpq::kWaves * kWave),
-                       p.lds1, st, a);
-    return check_launch("kmvq_gbar_kernel");
-  }
-  static const bool attr = hipFuncSetAttribute((const void*)mlpq::kmvq_grad_kernel<KD>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-  (void)attr;
+int launch_grad(const mlpq::Args& a, const QPlan& p, hipStream_t st) {
+  mlpq::allow_lds(mlpq::kmvq_grad_kernel<KD>);
   hipLaunchKernelGGL((mlpq::kmvq_grad_kernel<KD>), dim3((unsigned)p.n_blocks2), dim3(mlpq::kWaves2 * kWave), p.lds2,
                      st, a);
   return check_launch("kmvq_grad_kernel");
@@ -977,10 +871,7 @@ int q_launch(const mlpq::Args& a, const QPlan& p, hipStream_t st, int pass) {
 
 bool kmvq_supported(const pdeinv_kmv_mlp_desc* d) {
   if (d->impl == PDEINV_MLP_IMPL_PAIRS_RING) return false;  // explicit A/B selection of the register-ring kernels
-  if (!(d->dim >= 1 && d->dim <= 8 && d->width >= 1 && d->width <= mlpq::kW && d->n_layers >= 1 &&
-        d->n_layers <= mlpq::kLMax && d->out_features >= 1))
-    return false;
-  return q_plan(d).lds2 <= 160 * 1024;
+  return mlpq::tile_envelope(d->dim, d->n_layers, d->width, d->out_features) && q_plan(d).lds2 <= mlpq::kLdsMax;
 }
 
 size_t kmvq_workspace_bytes(const pdeinv_kmv_mlp_desc* d) { return q_plan(d).total; }
@@ -990,12 +881,29 @@ int kmvq_run(const pdeinv_kmv_mlp_desc* d, const float* z, int64_t set_stride, i
              const float* params, void* ws, double* acc, float* grad, float** gbar_out, int pass, hipStream_t st) {
   const QPlan p = q_plan(d);
   char* w = (char*)ws;
+  float* img = (float*)(w + p.off_img);
+  float* gbar = (float*)(w + p.off_gbar);
+  double* h0y0 = (double*)(w + p.off_h0);
+  if (gbar_out) *gbar_out = gbar;
+  const int L = d->n_layers;
+  if (pass == 0) {  // gbar_i = mean_j grad Phi(x_i - x_j) within each time stamp
+    int rc = mlpq::build_image(p.ip.ia, params, h0y0, img, st);
+    if (rc) return rc;
+    mlpq::PairForce f{};
+    f.x = f.r = z;
+    f.ldx = f.ldr = ld;
+    f.x_set = f.r_set = set_stride;
+    f.n_sets = d->n_sets;
+    f.n = f.m = d->n_rows;
+    f.gpart = (float*)(w + p.off_gpart);
+    f.net = mlpq::tile_net(p.ip, img);
+    rc = mlpq::pair_force_partials(f, st);
+    if (rc) return rc;
+    return mlpq::pair_force_reduce(f.gpart, p.items, p.n_ch, d->dim, 1.0 / (double)d->n_rows, gbar, st);
+  }
   mlpq::Args a{};
-  a.L = d->n_layers;
-  a.D = d->dim;
   a.n_ch = p.n_ch;
   a.n = d->n_rows;
-  a.n_items = p.items;
   a.n_units = p.n_units;
   a.set_stride = set_stride;
   a.ld = ld;
@@ -1003,49 +911,23 @@ int kmvq_run(const pdeinv_kmv_mlp_desc* d, const float* z, int64_t set_stride, i
   a.ds = ds;
   a.gamma = d->gamma;
   a.s = (float)(1.0 / ((double)d->n_rows * (double)d->n_rows * (double)d->n_sets));
-  a.inv_n = (float)(1.0 / (double)d->n_rows);
-  a.img = (const float*)(w + p.off_img);
-  a.img_floats = p.ia.img_floats;
-  for (int l = 0; l <= d->n_layers; ++l) {
-    a.fwd[l] = p.fwd[l];
-    a.bwd[l] = p.bwd[l];
-    a.bias[l] = p.ia.bias_off[l];
-    a.qoff[l] = (int)p.pm.poff[l];
-  }
-  a.fwd_out = p.fwd[d->n_layers];
-  a.h0_off = p.ia.h0_off;
-  a.bias_out = p.ia.bias_off[d->n_layers];
-  a.qoff_out = (int)p.pm.poff[d->n_layers];
+  a.net = mlpq::tile_net(p.ip, img);
+  for (int l = 0; l <= L; ++l) a.qoff[l] = (int)p.pm.poff[l];
+  a.qoff_out = (int)p.pm.poff[L];
   a.P = (int)p.P;
-  float* gbar = (float*)(w + p.off_gbar);
   a.gbar = gbar;
-  a.gpart = (float*)(w + p.off_gpart);
   a.gslab = (float*)(w + p.off_gslab);
   a.aslab = (float*)(w + p.off_aslab);
-  if (gbar_out) *gbar_out = gbar;
-  int rc = PDEINV_OK;
-  double* h0y0 = (double*)(w + p.off_h0);
-  if (pass == 0) {
-    rc = mlpq::build_image(p.ia, params, h0y0, (float*)(w + p.off_img), st);
-    if (rc) return rc;
-  }
-  rc = p.KD == 1 ? q_launch<1>(a, p, st, pass) : q_launch<2>(a, p, st, pass);
+  int rc = p.ip.KD == 1 ? launch_grad<1>(a, p, st) : launch_grad<2>(a, p, st);
   if (rc) return rc;
-  if (pass == 0) {
-    const int64_t nq = p.items * d->dim;
-    hipLaunchKernelGGL(mlpq::kmvq_gbar_reduce_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, a.gpart,
-                       p.items, p.n_ch, d->dim, a.inv_n, gbar);
-    return check_launch("kmvq_gbar_reduce_kernel");
-  }
   const int n_slabs = p.n_blocks2 * mlpq::kWaves2;
   hipLaunchKernelGGL(mlpq::kmvq_reduce_kernel, dim3((unsigned)((p.P + 255) / 256)), dim3(256), 0, st, p.pm, a.gslab,
                      n_slabs, p.P, a.aslab, (int64_t)n_slabs, grad, acc);
   rc = check_launch("kmvq_reduce_kernel");
   if (rc) return rc;
-  const int L = d->n_layers;
   hipLaunchKernelGGL(mlpq::kmvq_out_post_kernel, dim3(1), dim3(256), sizeof(double) * (size_t)d->out_features, st,
-                     a.gslab, n_slabs, p.P, a.qoff_out, d->width, d->out_features, params + p.ia.roff[L],
-                     (const double*)h0y0, grad + p.ia.roff[L]);
+                     a.gslab, n_slabs, p.P, a.qoff_out, d->width, d->out_features, params + p.ip.ia.roff[L],
+                     (const double*)h0y0, grad + p.ip.ia.roff[L]);
   return check_launch("kmvq_out_post_kernel");
 }
 

@@ -1,8 +1,11 @@
 // mlp_tile.h — the 16-row fp32-MFMA tile of the reference's narrow hypothesis nets (core/model.py:32-62:
 // tanh layers, Dense(40), sum of squares; dim <= 8, width <= 20 zero-padded to 20, 1 <= n_layers <= 8, any
-// out_features), shared by the KMV pair kernels (mlp_pairs_mfma.hip) and the learned-potential simulator and
-// batch evaluation (sde_mlp.hip): the P-layout helpers, the weight image's plan and builder, and the
-// value / input-gradient tile body (tile_grad) that both sde_mlp.hip kernels run.
+// out_features) and what every kernel built on it shares: the P-layout helpers, the weight image's plan and
+// builder, the value / input-gradient tile body (tile_grad), the pair force (the mean over a reference set of
+// grad Phi(x_i - r_j): chunk partials and their reduce) and the host side of a tile kernel (envelope, workspace
+// plan, CU count, dynamic-LDS limit). tile_grad runs in the pair-force kernel (mlp_pairs_mfma.hip: pass 0 of the
+// KMV residual and the learned interaction of sde_mf_mlp.hip) and in both kernels of sde_mlp.hip; pass 2 of the
+// residual (kmvq_grad_kernel, mlp_pairs_mfma.hip) carries four Taylor streams through its own tile body.
 //
 // Layout (see mlp_pairs_mfma.hip for the full account). Every activation tile is the C/D fragment of a
 // v_mfma_f32_16x16x4_f32: the row (pair / particle) on lane & 15, the feature on (lane >> 4, register) — the
@@ -18,6 +21,7 @@ namespace mlpq {
 constexpr int kW = 20;       // padded hidden width
 constexpr int kNS = 5;       // compact slots of a hidden stream
 constexpr int kLMax = 8;     // hidden (tanh) layers
+constexpr int kChunk = 256;  // references per work unit of the pair force (16 tiles)
 
 // feature carried by compact slot k in lane group g, for a stream of ns slots
 __host__ __device__ inline int slot_feat(int ns, int k, int g) {
@@ -69,6 +73,19 @@ __device__ __forceinline__ void lane_dims(const float* row, int D, int g, float 
   for (int kk = 0; kk < KD; ++kk) {
     const int k = 4 * kk + g;
     x[kk] = k < D ? row[k] : 0.f;
+  }
+}
+
+// Reference row j of a chunk ending at j_end, coordinates 4 kk + g: an unconditional load from a clamped
+// (row, coordinate), always inside r, masked after the load (0 past j_end and past D).
+template <int KD>
+__device__ __forceinline__ void load_ref(const float* r, int64_t ld, int D, int g, int64_t j, int64_t j_end,
+                                         float (&xn)[KD]) {
+#pragma unroll
+  for (int kk = 0; kk < KD; ++kk) {
+    const int k = 4 * kk + g;
+    const float v = r[(j < j_end ? j : j_end - 1) * ld + (k < D ? k : D - 1)];
+    xn[kk] = (j < j_end && k < D) ? v : 0.f;
   }
 }
 
@@ -160,10 +177,15 @@ inline TileNet tile_net(const ImagePlan& p, const float* img) {
   return t;
 }
 
-// V(x) and grad V(x) of the 16 rows of a tile (the tile body of pass 1 of the KMV pair kernels, per row instead
-// of summed over pairs). img: the LDS copy of the image. x: the row's coordinates 4 kk + g on lane (row, g)
-// (lane_dims; zero past D). Returns the last backward product's C fragment: register r of lane (row, g) is
-// d V / d x_{4 g + r} of the row (zero past D). VALUE: `value` = V of the lane's row (the same on its four lane
+// the block's LDS copy of the image (the caller synchronises before the first read)
+__device__ __forceinline__ void stage_image(f32x4* lds4, const TileNet& net) {
+  const f32x4* src = reinterpret_cast<const f32x4*>(net.img);
+  for (int q = threadIdx.x; q < net.img_floats / 4; q += blockDim.x) lds4[q] = src[q];
+}
+
+// V(x) and grad V(x) of the 16 rows of a tile. img: the LDS copy of the image. x: the row's coordinates
+// 4 kk + g on lane (row, g) (lane_dims; zero past D). Returns the last backward product's C fragment: register r
+// of lane (row, g) is d V / d x_{4 g + r} of the row (zero past D). VALUE: `value` = V of the lane's row (the same on its four lane
 // groups), from the folded output layer V = dh^T M dh + 2 c0^T dh + |y0|^2, dh = h - h0.
 // `lane` must be opaque to the compiler inside a loop (asm volatile "+v"): the weight fragments are the same for
 // every tile and step, and a visible lane index lets the compiler hoist all of them (hundreds of VGPRs).
@@ -263,6 +285,77 @@ __device__ __forceinline__ f32x4 tile_grad(const float* img, const TileNet& t, i
     for (int kk = 0; kk < kNS; ++kk) gacc = mfma(w[kk], zb[kk], gacc);
   }
   return gacc;
+}
+
+// -------------------------------------------------------------------------------------------------
+// pair force: gpart[it][ch][D] = sum over chunk ch of the references of grad Phi(x_i - r_j)
+// -------------------------------------------------------------------------------------------------
+// n_sets sets of n items x against their set's m references r (rows of pitch ldx / ldr, sets x_set / r_set floats
+// apart); item it = t * n + i. The chunk grid is fixed by the reference index: an item's numbers depend on its own
+// row and on its reference set in its order only, not on n, on the items that share the call or on the launch.
+struct PairForce {
+  const float *x, *r;
+  int64_t ldx, ldr, x_set, r_set, n_sets, n, m;
+  float* gpart;  // [n_sets * n][pair_chunks(m)][D]
+  TileNet net;
+};
+__host__ __device__ inline int pair_chunks(int64_t m) { return (int)((m + kChunk - 1) / kChunk); }
+// the partials on the stream (the image is in place); the launcher owns the grid, the LDS size and its limit
+int pair_force_partials(const PairForce& f, hipStream_t st);
+// out[it][k] = inv_m sum_ch gpart[it][ch][k] (reduce_chunks), one thread per coordinate
+int pair_force_reduce(const float* gpart, int64_t n_items, int n_ch, int D, double inv_m, float* out, hipStream_t st);
+
+// coordinate k of item `it`: inv_m sum_ch gpart[it][ch][k], chunks in order, fp64
+__device__ __forceinline__ float reduce_chunks(const float* __restrict__ gpart, int64_t it, int n_ch, int D, int k,
+                                               double inv_m) {
+  double s = 0.0;
+  for (int c = 0; c < n_ch; ++c) s += (double)gpart[(it * n_ch + c) * D + k];
+  return (float)(s * inv_m);
+}
+
+// -------------------------------------------------------------------------------------------------
+// host side of a tile kernel
+// -------------------------------------------------------------------------------------------------
+inline bool tile_shape_ok(int dim, int n_layers, int width, int out_features) {
+  return dim >= 1 && n_layers >= 1 && width >= 1 && out_features >= 1;
+}
+inline bool tile_envelope(int dim, int n_layers, int width, int out_features) {
+  return tile_shape_ok(dim, n_layers, width, out_features) && dim <= 8 && width <= kW && n_layers <= kLMax;
+}
+inline bool tile_shape_ok(const pdeinv_mlp_shape* s) {
+  return tile_shape_ok(s->dim, s->n_layers, s->width, s->out_features);
+}
+inline bool tile_envelope(const pdeinv_mlp_shape* s) {
+  return tile_envelope(s->dim, s->n_layers, s->width, s->out_features);
+}
+
+int device_cus();  // compute units of the current device (256 if the query fails)
+
+// Dynamic LDS above the default limit, up to the CU's 160 KiB: set at every launch (a "done once" flag per
+// kernel type would be shared by kernels of one signature).
+constexpr size_t kLdsMax = 160 * 1024;
+template <typename K>
+inline void allow_lds(K kernel) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax);
+}
+
+// workspaces are cut into 256-byte pieces: the offset of the next piece of `bytes`, `end` moved past it
+inline size_t take(size_t& end, size_t bytes) {
+  const size_t at = end;
+  end += (bytes + 255) & ~(size_t)255;
+  return at;
+}
+// workspace of a tile kernel: [image | h0y0 (W + O doubles)]; a caller may append to `total`
+struct TileWs {
+  ImagePlan ip;
+  size_t off_img, off_h0, total;
+};
+inline TileWs tile_ws(const pdeinv_mlp_shape* s) {
+  TileWs w{};
+  w.ip = image_plan(s->dim, s->n_layers, s->width, s->out_features);
+  w.off_img = take(w.total, sizeof(float) * (size_t)w.ip.ia.img_floats);
+  w.off_h0 = take(w.total, sizeof(double) * (size_t)(s->width + s->out_features));
+  return w;
 }
 
 }  // namespace mlpq

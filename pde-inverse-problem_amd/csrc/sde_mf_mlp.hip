@@ -6,23 +6,19 @@
 //                         the references being the gathered positions of the whole ensemble (all ranks);
 //   pdeinv_mf_mlp_prepare the weight image, once per simulate, into the workspace the steps read.
 //
-// Force kernel. The layout of pass 1 of the KMV residual (kmvq_gbar_kernel, mlp_pairs_mfma.hip) with separate item
-// and reference sets: a wave owns one (item, chunk of kChunk references by reference index) unit, walks the chunk in
-// 16-pair tiles — the pair on lane & 15, y = x_i - r_j formed in fp32 — and runs mlpq::tile_grad on each (every
-// product a v_mfma_f32_16x16x4_f32, the weight image staged once per persistent block). The tile gradients of a lane
-// add up in registers in tile order, the 16 lanes of a coordinate fold in a fixed butterfly, and the unit's D sums
-// go to gpart[item][chunk]. No atomics. Tail tiles and the short last chunk load from a clamped row index (always
-// inside r) and are masked after the load; their pairs run the tile at y = 0 and are dropped by a select.
-// An item's numbers depend on its own row and on the reference set in its order only: the chunk grid is fixed by the
+// Force. The pair-force kernel of mlp_pairs_mfma.hip (mlpq::pair_force_partials, which is also the gbar pass of the
+// KMV residual) with one set of items against one set of references: a wave per (item, chunk of kChunk references by
+// reference index), mlpq::tile_grad on each 16-pair tile, the unit's D sums to gpart[item][chunk]. No atomics. An
+// item's numbers depend on its own row and on the reference set in its order only: the chunk grid is fixed by the
 // reference index, not by n, by the items that share the call, or by the launch grid.
 //
-// Reduce / step. The chunk partials of an item are summed in chunk order in fp64 and scaled by 1/m (reduce_chunks:
-// what kmvq_gbar_reduce_kernel does). The batch entry does that in a small kernel of its own; the simulator's step
-// does it at the head of the update kernel instead of through a force array: the update is one thread per particle
-// with 2d floats of state, so the fused form saves a launch and a round trip of [N, d] per update and costs nothing
-// (n_ch <= 20 partials per coordinate at N = 5000). Both call the same function, so the step's force is the batch
-// entry's bit for bit. The update itself is mf_step_kernel's (sde.hip): the Philox stream of include/pdeinv.h through
-// stream_normals with the global id as the counter, explicit d_noise honoured, the shared clock tau0 of the
+// Reduce / step. The chunk partials of an item are summed in chunk order in fp64 and scaled by 1/m
+// (mlpq::reduce_chunks). The batch entry does that in the small kernel of mlpq::pair_force_reduce; the simulator's
+// step does it at the head of the update kernel instead of through a force array: the update is one thread per
+// particle with 2d floats of state, so the fused form saves a launch and a round trip of [N, d] per update and costs
+// nothing (n_ch <= 20 partials per coordinate at N = 5000). Both call the same function, so the step's force is the
+// batch entry's bit for bit. The update itself is mf_step_kernel's (sde.hip): the Philox stream of include/pdeinv.h
+// through stream_normals with the global id as the counter, explicit d_noise honoured, the shared clock tau0 of the
 // ensemble (shared_tau0_host), h = tau0 / dt / dt - tau0.
 #include <math.h>
 
@@ -34,91 +30,6 @@ namespace pdeinv {
 namespace mlpmf {
 
 using namespace mlpq;
-
-constexpr int kWavesB = 8;  // waves per block: two blocks per CU = 4 waves per SIMD
-constexpr int kThreads = kWavesB * kWave;
-constexpr int kChunk = 256;  // references per work unit (16 tiles): pass 1's
-
-struct ForceArgs {
-  int64_t n, m, ldx, ldr, n_units;
-  int32_t n_ch;
-  const float* x;
-  const float* r;
-  float* gpart;  // [n][n_ch][D]
-  TileNet net;
-};
-
-template <int KD>
-__global__ __launch_bounds__(kThreads, 2) void mf_mlp_force_kernel(ForceArgs a) {
-  extern __shared__ f32x4 lds4[];
-  float* img = reinterpret_cast<float*>(lds4);
-  for (int q = threadIdx.x; q < a.net.img_floats / 4; q += blockDim.x)
-    lds4[q] = reinterpret_cast<const f32x4*>(a.net.img)[q];
-  __syncthreads();
-  const int lane0 = threadIdx.x & (kWave - 1), p = lane0 & 15, g = lane0 >> 4;
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int64_t wave = (int64_t)blockIdx.x * kWavesB + wib;
-  const int64_t n_waves = (int64_t)gridDim.x * kWavesB;
-  const int D = a.net.D;
-  for (int64_t unit = wave; unit < a.n_units; unit += n_waves) {
-    const int64_t it = unit / a.n_ch, ch = unit - it * a.n_ch;
-    const int64_t j_end = (ch + 1) * kChunk < a.m ? (ch + 1) * kChunk : a.m;
-    float xi[KD];
-    lane_dims<KD>(a.x + it * a.ldx, D, g, xi);
-    // reference row j of this lane's coordinates: an unconditional load from a clamped (row, coordinate), masked after
-    auto load_ref = [&](int64_t j, float (&xn)[KD]) {
-#pragma unroll
-      for (int kk = 0; kk < KD; ++kk) {
-        const int k = 4 * kk + g;
-        const float v = a.r[(j < j_end ? j : j_end - 1) * a.ldr + (k < D ? k : D - 1)];
-        xn[kk] = (j < j_end && k < D) ? v : 0.f;
-      }
-    };
-    f32x4 gacc = {};
-    float xn[KD];
-    load_ref(ch * kChunk + p, xn);
-    for (int64_t j0 = ch * kChunk; j0 < j_end; j0 += 16) {
-      // the weight fragments are the same for every tile: an opaque lane index keeps the compiler from hoisting
-      // all of them out of the tile loop (hundreds of VGPRs)
-      int lane = lane0;
-      asm volatile("" : "+v"(lane));
-      const bool active = j0 + p < j_end;
-      float yb[KD];
-#pragma unroll
-      for (int kk = 0; kk < KD; ++kk) yb[kk] = (active && 4 * kk + g < D) ? xi[kk] - xn[kk] : 0.f;
-      load_ref(j0 + 16 + p, xn);  // the next tile's rows, under this tile's products
-      float unused;
-      const f32x4 ga = tile_grad<KD, false>(img, a.net, lane, yb, unused);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) gacc[r] += active ? ga[r] : 0.f;
-    }
-    // sum over the 16 pairs of the lane row, coordinates 4 g + r
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float v = gacc[r];
-#pragma unroll
-      for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 16);
-      const int k = 4 * g + r;
-      if (p == 0 && k < D) a.gpart[unit * D + k] = v;
-    }
-  }
-}
-
-// coordinate k of item `it`: inv_m sum_ch gpart[it][ch][k], chunks in order, fp64
-__device__ __forceinline__ float reduce_chunks(const float* __restrict__ gpart, int64_t it, int n_ch, int D, int k,
-                                               double inv_m) {
-  double s = 0.0;
-  for (int c = 0; c < n_ch; ++c) s += (double)gpart[(it * n_ch + c) * D + k];
-  return (float)(s * inv_m);
-}
-
-__global__ __launch_bounds__(kBlock) void mf_mlp_reduce_kernel(const float* __restrict__ gpart, int64_t n, int n_ch,
-                                                               int D, double inv_m, float* __restrict__ force) {
-  const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (q >= n * D) return;
-  const int64_t it = q / D;
-  force[q] = reduce_chunks(gpart, it, n_ch, D, (int)(q - it * D), inv_m);
-}
 
 struct StepArgs {
   int64_t N, poff, ld_z;
@@ -165,65 +76,39 @@ __global__ __launch_bounds__(kBlock) void mf_mlp_step_kernel(StepArgs a, const f
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-static bool shape_ok(const pdeinv_mlp_shape* s) {
-  return s->dim >= 1 && s->n_layers >= 1 && s->width >= 1 && s->out_features >= 1;
-}
-static bool tile_envelope(const pdeinv_mlp_shape* s) {
-  return shape_ok(s) && s->dim <= 8 && s->width <= kW && s->n_layers <= kLMax;
-}
 static const char* const kEnvelope =
     "mf_mlp: the learned-interaction kernels cover dim <= 8, width <= 20, 1 <= n_layers <= 8";
 
-static int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  return cus;
-}
-
-// workspace: [image | h0y0 (W + O doubles) | gpart (n items x n_ch x D floats)], 256-byte pieces
+// workspace: the tile kernels' [image | h0y0] and gpart (n items x n_ch x D floats)
 struct Ws {
-  ImagePlan ip;
+  TileWs t;
   int n_ch;
-  size_t off_img, off_h0, off_gpart, total, lds;
+  size_t off_gpart, total;
 };
 static Ws ws_plan(const pdeinv_mlp_shape* s, int64_t n, int64_t m) {
   Ws w{};
-  w.ip = image_plan(s->dim, s->n_layers, s->width, s->out_features);
-  w.n_ch = (int)((m + kChunk - 1) / kChunk);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-  w.off_img = take(sizeof(float) * (size_t)w.ip.ia.img_floats);
-  w.off_h0 = take(sizeof(double) * (size_t)(s->width + s->out_features));
-  w.off_gpart = take(sizeof(float) * (size_t)n * (size_t)w.n_ch * (size_t)s->dim);
-  w.total = o;
-  w.lds = sizeof(float) * (size_t)w.ip.ia.img_floats;
+  w.t = tile_ws(s);
+  w.n_ch = pair_chunks(m);
+  w.total = w.t.total;
+  w.off_gpart = take(w.total, sizeof(float) * (size_t)n * (size_t)w.n_ch * (size_t)s->dim);
   return w;
 }
 
+// the image of this call's parameters into the workspace
+static int image_into(const Ws& w, void* ws, const float* params, hipStream_t st) {
+  return build_image(w.t.ip.ia, params, (double*)((char*)ws + w.t.off_h0), (float*)((char*)ws + w.t.off_img), st);
+}
+
 // the chunk partials of items x [n] against references r [m] into the workspace's gpart (the image is in place)
-static int launch_force(const Ws& w, void* ws, const float* x, int64_t n, int64_t ldx, const float* r, int64_t m,
-                        int64_t ldr, hipStream_t st) {
-  ForceArgs a{};
-  a.n = n; a.m = m; a.ldx = ldx; a.ldr = ldr;
-  a.n_ch = w.n_ch;
-  a.n_units = n * w.n_ch;
-  a.x = x; a.r = r;
-  a.gpart = (float*)((char*)ws + w.off_gpart);
-  a.net = tile_net(w.ip, (const float*)((char*)ws + w.off_img));
-  const int64_t need = (a.n_units + kWavesB - 1) / kWavesB, cap = 2 * (int64_t)device_cus();
-  const dim3 gr((unsigned)(need < cap ? need : cap)), bl(kThreads);
-  if (w.ip.KD == 1) {
-    (void)hipFuncSetAttribute((const void*)mf_mlp_force_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    hipLaunchKernelGGL(mf_mlp_force_kernel<1>, gr, bl, w.lds, st, a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)mf_mlp_force_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    hipLaunchKernelGGL(mf_mlp_force_kernel<2>, gr, bl, w.lds, st, a);
-  }
-  return check_launch("mf_mlp_force_kernel");
+static int force_partials(const Ws& w, void* ws, const float* x, int64_t n, int64_t ldx, const float* r, int64_t m,
+                          int64_t ldr, hipStream_t st) {
+  PairForce f{};
+  f.x = x; f.r = r;
+  f.ldx = ldx; f.ldr = ldr;
+  f.n_sets = 1; f.n = n; f.m = m;
+  f.gpart = (float*)((char*)ws + w.off_gpart);
+  f.net = tile_net(w.t.ip, (const float*)((char*)ws + w.t.off_img));
+  return pair_force_partials(f, st);
 }
 
 }  // namespace mlpmf
@@ -242,7 +127,7 @@ extern "C" size_t pdeinv_mf_mlp_workspace_bytes(const pdeinv_mlp_shape* s, int64
 // the checks shared by the three entry points (before any device call)
 static int check_shape_ws(const pdeinv_mlp_shape* s, const void* ws, bool need_ws) {
   PDEINV_REQUIRE(s != nullptr, PDEINV_ERR_INVALID, "mf_mlp: null shape");
-  PDEINV_REQUIRE(shape_ok(s), PDEINV_ERR_INVALID, "mf_mlp: dim, n_layers, width and out_features must be >= 1");
+  PDEINV_REQUIRE(tile_shape_ok(s), PDEINV_ERR_INVALID, "mf_mlp: dim, n_layers, width and out_features must be >= 1");
   PDEINV_REQUIRE(tile_envelope(s), PDEINV_ERR_UNSUPPORTED, kEnvelope);
   if (need_ws)
     PDEINV_REQUIRE(ws != nullptr && (uintptr_t)ws % 256 == 0, PDEINV_ERR_INVALID,
@@ -255,9 +140,8 @@ extern "C" int pdeinv_mf_mlp_prepare(const pdeinv_mlp_shape* s, const float* par
   if (rc) return rc;
   PDEINV_REQUIRE(params != nullptr && aligned(params, 4), PDEINV_ERR_INVALID,
                  "mf_mlp_prepare: params is null or unaligned");
-  const Ws w = ws_plan(s, 0, 1);  // the image and h0y0 offsets do not depend on n, m
-  return build_image(w.ip.ia, params, (double*)((char*)ws + w.off_h0), (float*)((char*)ws + w.off_img),
-                     (hipStream_t)stream);
+  // (the image and h0y0 offsets do not depend on n, m)
+  return image_into(ws_plan(s, 0, 1), ws, params, (hipStream_t)stream);
 }
 
 extern "C" int pdeinv_mf_mlp_force(const pdeinv_mlp_shape* s, const float* params, const float* x, int64_t n,
@@ -278,14 +162,11 @@ extern "C" int pdeinv_mf_mlp_force(const pdeinv_mlp_shape* s, const float* param
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const Ws w = ws_plan(s, n, m);
-  rc = build_image(w.ip.ia, params, (double*)((char*)ws + w.off_h0), (float*)((char*)ws + w.off_img), st);
+  rc = image_into(w, ws, params, st);
   if (rc) return rc;
-  rc = launch_force(w, ws, x, n, lx, r, m, lr, st);
+  rc = force_partials(w, ws, x, n, lx, r, m, lr, st);
   if (rc) return rc;
-  const int64_t nq = n * s->dim;
-  hipLaunchKernelGGL(mf_mlp_reduce_kernel, dim3((unsigned)((nq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-                     (const float*)((char*)ws + w.off_gpart), n, w.n_ch, (int)s->dim, 1.0 / (double)m, force);
-  return check_launch("mf_mlp_reduce_kernel");
+  return pair_force_reduce((const float*)((char*)ws + w.off_gpart), n, w.n_ch, s->dim, 1.0 / (double)m, force, st);
 }
 
 extern "C" int pdeinv_mf_mlp_step(const pdeinv_sde_desc* d, const pdeinv_mlp_shape* s, int32_t step, const float* z,
@@ -318,7 +199,7 @@ extern "C" int pdeinv_mf_mlp_step(const pdeinv_sde_desc* d, const pdeinv_mlp_sha
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const Ws w = ws_plan(s, sa.N, m);
-  rc = launch_force(w, ws, z, sa.N, sa.ld_z0, ref, m, lr, st);
+  rc = force_partials(w, ws, z, sa.N, sa.ld_z0, ref, m, lr, st);
   if (rc) return rc;
   StepArgs a{};
   a.N = sa.N; a.poff = sa.poff; a.ld_z = sa.ld_z0;

@@ -48,11 +48,6 @@ struct SimArgs {
   TileNet net;
 };
 
-__device__ __forceinline__ void stage_image(f32x4* lds4, const TileNet& net) {
-  for (int q = threadIdx.x; q < net.img_floats / 4; q += blockDim.x) lds4[q] = reinterpret_cast<const f32x4*>(net.img)[q];
-  __syncthreads();
-}
-
 // The tile's rows [16][M] (M = 2d floats, assembled in `slot`) -> dst, whole rows, n_valid of them: 16-byte pieces
 // when M % 4 == 0 (rows then start on 16-byte boundaries), 8-byte pieces otherwise (M is even).
 __device__ __forceinline__ void store_tile(float* dst, const float* slot, int M, int lane, int n_valid) {
@@ -78,6 +73,7 @@ __global__ __launch_bounds__(kThreads) void sde_mlp_kernel(SimArgs a, const floa
   extern __shared__ f32x4 lds4[];
   float* img = reinterpret_cast<float*>(lds4);
   stage_image(lds4, a.net);
+  __syncthreads();
   const int lane0 = threadIdx.x & (kWave - 1), p = lane0 & 15, g = lane0 >> 4;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   float* gslot = img + a.net.img_floats + wib * kSlot;
@@ -185,6 +181,7 @@ __global__ __launch_bounds__(kThreads) void mlp_potential_kernel(TileNet net, co
   extern __shared__ f32x4 lds4[];
   float* img = reinterpret_cast<float*>(lds4);
   stage_image(lds4, net);
+  __syncthreads();
   const int lane0 = threadIdx.x & (kWave - 1), p = lane0 & 15, g = lane0 >> 4;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
   const int D = net.D;
@@ -212,46 +209,14 @@ __global__ __launch_bounds__(kThreads) void mlp_potential_kernel(TileNet net, co
 }
 
 // ---- host ----------------------------------------------------------------------------------------
-static bool shape_ok(const pdeinv_mlp_shape* s) {
-  return s->dim >= 1 && s->n_layers >= 1 && s->width >= 1 && s->out_features >= 1;
-}
-static bool tile_envelope(const pdeinv_mlp_shape* s) {
-  return shape_ok(s) && s->dim <= 8 && s->width <= kW && s->n_layers <= kLMax;
-}
-
-static int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  return cus;
-}
-
-// workspace of the tile path: [image | h0y0 (W + O doubles)], 256-byte pieces
-struct TileWs {
-  ImagePlan ip;
-  size_t off_img, off_h0, total, lds;
-};
-static TileWs tile_ws(const pdeinv_mlp_shape* s) {
-  TileWs w{};
-  w.ip = image_plan(s->dim, s->n_layers, s->width, s->out_features);
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
-  w.off_img = take(sizeof(float) * (size_t)w.ip.ia.img_floats);
-  w.off_h0 = take(sizeof(double) * (size_t)(s->width + s->out_features));
-  w.total = o;
-  w.lds = sizeof(float) * ((size_t)w.ip.ia.img_floats + (size_t)kWavesB * kSlot);
-  return w;
+// dynamic LDS of both kernels: the image and the waves' slots
+static size_t lds_bytes(const TileWs& w) {
+  return sizeof(float) * ((size_t)w.ip.ia.img_floats + (size_t)kWavesB * kSlot);
 }
 
 static int grid_of(int64_t n_tiles) {
   const int64_t need = (n_tiles + kWavesB - 1) / kWavesB, cap = 2 * (int64_t)device_cus();
   return (int)(need < cap ? need : cap);
-}
-
-template <typename K>
-static void allow_lds(K kernel) {
-  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 }  // namespace mlps
@@ -261,7 +226,7 @@ using namespace pdeinv;
 using namespace pdeinv::mlps;
 
 extern "C" int pdeinv_mlp_potential_path(const pdeinv_mlp_shape* s) {
-  if (!s || !shape_ok(s)) return 0;
+  if (!s || !tile_shape_ok(s)) return 0;
   if (tile_envelope(s)) return 2;
   return pdeinv_mlp_fused_supported(s->dim, s->n_layers, s->width, s->out_features) ? 1 : 0;
 }
@@ -277,7 +242,7 @@ extern "C" size_t pdeinv_mlp_potential_workspace_bytes(const pdeinv_mlp_shape* s
 extern "C" int pdeinv_mlp_potential(const pdeinv_mlp_shape* s, const float* params, const float* x, int64_t n,
                                     int64_t ld, float* value, float* grad, void* ws, void* stream) {
   PDEINV_REQUIRE(s != nullptr, PDEINV_ERR_INVALID, "mlp_potential: null shape");
-  PDEINV_REQUIRE(shape_ok(s), PDEINV_ERR_INVALID,
+  PDEINV_REQUIRE(tile_shape_ok(s), PDEINV_ERR_INVALID,
                  "mlp_potential: dim, n_layers, width and out_features must be >= 1");
   const int path = pdeinv_mlp_potential_path(s);
   PDEINV_REQUIRE(path != 0, PDEINV_ERR_UNSUPPORTED,
@@ -299,12 +264,13 @@ extern "C" int pdeinv_mlp_potential(const pdeinv_mlp_shape* s, const float* para
   const TileNet net = tile_net(w.ip, img);
   const int64_t n_tiles = (n + 15) / 16;
   const dim3 gr((unsigned)grid_of(n_tiles)), bl(kThreads);
+  const size_t lds = lds_bytes(w);
   if (w.ip.KD == 1) {
     allow_lds(mlp_potential_kernel<1>);
-    hipLaunchKernelGGL(mlp_potential_kernel<1>, gr, bl, w.lds, st, net, x, n, ldx, n_tiles, value, grad);
+    hipLaunchKernelGGL(mlp_potential_kernel<1>, gr, bl, lds, st, net, x, n, ldx, n_tiles, value, grad);
   } else {
     allow_lds(mlp_potential_kernel<2>);
-    hipLaunchKernelGGL(mlp_potential_kernel<2>, gr, bl, w.lds, st, net, x, n, ldx, n_tiles, value, grad);
+    hipLaunchKernelGGL(mlp_potential_kernel<2>, gr, bl, lds, st, net, x, n, ldx, n_tiles, value, grad);
   }
   return check_launch("mlp_potential_kernel");
 }
@@ -325,7 +291,8 @@ extern "C" int pdeinv_sde_simulate_mlp(const pdeinv_sde_desc* d, const pdeinv_ml
   PDEINV_REQUIRE(s != nullptr, PDEINV_ERR_INVALID, "sde_mlp: null shape");
   PDEINV_REQUIRE(d->potential.kind == PDEINV_POT_MLP, PDEINV_ERR_INVALID,
                  "sde_mlp: potential kind must be PDEINV_POT_MLP");
-  PDEINV_REQUIRE(shape_ok(s), PDEINV_ERR_INVALID, "sde_mlp: dim, n_layers, width and out_features must be >= 1");
+  PDEINV_REQUIRE(tile_shape_ok(s), PDEINV_ERR_INVALID,
+                 "sde_mlp: dim, n_layers, width and out_features must be >= 1");
   PDEINV_REQUIRE(tile_envelope(s), PDEINV_ERR_UNSUPPORTED,
                  "sde_mlp: the learned-potential simulator covers dim <= 8, width <= 20, 1 <= n_layers <= 8");
   PDEINV_REQUIRE(d->dim == s->dim, PDEINV_ERR_INVALID, "sde_mlp: descriptor and shape disagree on dim");
@@ -356,10 +323,11 @@ extern "C" int pdeinv_sde_simulate_mlp(const pdeinv_sde_desc* d, const pdeinv_ml
   a.noise = sa.noise; a.shift_u = sa.shift_u;
   a.net = tile_net(w.ip, img);
   const dim3 gr((unsigned)grid_of(a.n_tiles)), bl(kThreads);
+  const size_t lds = lds_bytes(w);
 #define LAUNCH(KD, EX)                                                                                      \
   do {                                                                                                      \
     allow_lds(sde_mlp_kernel<KD, EX>);                                                                      \
-    hipLaunchKernelGGL((sde_mlp_kernel<KD, EX>), gr, bl, w.lds, st, a, z0, traj, tau, last);                \
+    hipLaunchKernelGGL((sde_mlp_kernel<KD, EX>), gr, bl, lds, st, a, z0, traj, tau, last);                  \
   } while (0)
   if (w.ip.KD == 1) {
     if (a.noise) LAUNCH(1, true); else LAUNCH(1, false);

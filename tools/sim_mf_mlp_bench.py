@@ -7,9 +7,8 @@ same run:
 * a torch autograd loop of the same system (V_hypothesis.apply on the pair differences + torch.autograd.grad + the
   element-wise update, torch.randn noise), the pairs taken in item blocks to bound its memory, over `--torch-steps`
   updates (it is about two orders slower), reported per update;
-* the KMV residual's pass 0 (kmvq_gbar_kernel + its reduce) for the same pair count: pdeinv_residual_kmv_mlp on one
-  time stamp of the same 5000 rows, its pass-0 kernels' device time read from the torch profiler's kernel records
-  (the residual has no pass-0 entry point of its own); the whole residual call is timed by events as well.
+* the KMV residual (pdeinv_residual_kmv_mlp) on one time stamp of the same 5000 rows, whose pass 0 is the same
+  pair-force kernel on the same pair count; the whole call is timed by events.
 
 The variants are timed alternately (one round = each variant once, between two device events after a synchronise),
 after a warm-up of each; reported: the median over the rounds and the spread. Also the issue model of DESIGN.md:
@@ -36,20 +35,6 @@ def mfma_per_tile(d: int, L: int) -> int:
     """16x16x4 MFMAs of one tile_grad call (mlp_tile.h), as tools/sim_mlp_bench.py counts them."""
     kd = 1 if d <= 4 else 2
     return 2 * kd + 10 * (L - 1) + 10 + 10 * (L - 1) + 5
-
-
-def pass0_kernel_ms(fn, reps: int):
-    """Device time per call of the kernels whose name holds `kmvq_gbar` (pass 0 and its reduce) inside fn()."""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CUDA]) as prof:
-        for _ in range(reps):
-            fn()
-        torch.cuda.synchronize()
-    us = [e.device_time_total if hasattr(e, "device_time_total") else e.cuda_time_total
-          for e in prof.events() if "kmvq_gbar" in e.name]
-    if not us:
-        raise RuntimeError("the profiler recorded no kmvq_gbar kernel")
-    return sum(us) / 1e3 / reps
 
 
 def main():
@@ -152,22 +137,10 @@ def main():
     res["hip_force_batch_over_model"] = res["hip_force_batch"]["median_ms"] / model_ms
     res["torch_ms_per_update"] = torch_per_update
     res["torch_over_hip_per_update"] = torch_per_update / per_update
-
-    def dump():
-        os.makedirs(os.path.dirname(a.out), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
-            f.write("\n")
-
-    res["residual_pass0_ms"], res["residual_pass0_note"] = None, "not measured yet"
-    dump()  # the event timings are on disk before the profiler runs
-    try:
-        pass0_ms, note = pass0_kernel_ms(residual, 3), "torch profiler kernel records, mean of 3 calls"
-    except Exception as e:  # the profiler is not part of the package: say so in the record, keep the rest
-        pass0_ms, note = None, f"not measured: {type(e).__name__}: {e}"
-    res["residual_pass0_ms"], res["residual_pass0_note"] = pass0_ms, note
-    res["hip_per_update_over_residual_pass0"] = per_update / pass0_ms if pass0_ms else None
-    dump()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
     print(json.dumps(res))
 
 
