@@ -126,7 +126,8 @@ def _coef(d, tau):
 
 def test_kmv_weights_d8(native):
     """kmv_weights_kernel<8>: per-particle (d_s log rho, d_s^2 log rho) vs the fp64 restatement
-    (…_quadratic.py:18-191) and the per-stamp c-weighted moments (c = ds2 + ds^2 + gamma ds)."""
+    (…_quadratic.py:18-191) and the per-stamp c-weighted moments (c = ds2 + ds^2 + gamma ds).
+    Every compiled dimension against fp64 at a per-entry fp32 tolerance: tests/test_gpu_kmv_sums.py."""
     d, n = 8, 2500
     tau = [0.3, 1.1, 1.9]
     cfg, coef = _coef(d, tau)
@@ -147,7 +148,8 @@ def test_kmv_weights_d8(native):
 @pytest.mark.parametrize("d,n_t,n", [(8, 7, 50_001), (2, 3, 999), (5, 2, 4096)])
 def test_kmv_moments_weights_fused_equals_separate(native, d, n_t, n):
     """The fused one-read pass == moments_batched(2d) + kmv_weights(d) on the same rows (the sums are
-    reassociated differently: 1e-5 relative)."""
+    reassociated differently: 1e-5 relative).
+    HIP against HIP; each kernel against fp64, entry by entry: tests/test_gpu_kmv_sums.py."""
     rng = np.random.default_rng(d + n)
     tau = np.linspace(0.2, 1.8, n_t)
     _, coef = _coef(d, tau)
@@ -247,7 +249,8 @@ def test_simulate_mf_kmv_equals_separate(native, d, n, n_steps, poff):
     mom / wst == kmv_moments_weights over the written trajectory to fp32 reassociation (1e-5 relative, as
     test_kmv_moments_weights_fused_equals_separate); with the next simulate, sums_next as
     test_simulate_mf_next_sums. Partial waves (n = 37), rows past N inside a block (4099, 999), ids past 2^32,
-    one stamp (n_steps = 1), three running noise sums per lane (n_steps + 1 = 128)."""
+    one stamp (n_steps = 1), three running noise sums per lane (n_steps + 1 = 128).
+    HIP against HIP; the simulator's sums against fp64, entry by entry: tests/test_gpu_kmv_sums.py."""
     rng = np.random.default_rng(d + n + n_steps + 1)
     z0 = _t(rng.standard_normal((n, 2 * d)) * 0.8 + 0.25)
     A = nr.problem_constants(d)

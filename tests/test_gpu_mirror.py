@@ -56,7 +56,8 @@ def test_kmv_sde_stamp_sums_product_path(native, d):
     from the simulator (simulate_interacting(stamp_sums=True): pdeinv_sde_simulate_mf_kmv, no trajectory written),
     value_and_grad_fn consumes data["kmv_sums"]; the same simulate with its trajectory written and the residual's own
     pass over it gives the same loss / loss ground truth / gradient (fp32 reassociation: 1e-5 relative) and the same
-    stamps."""
+    stamps.
+    Two routes through the same kernels; each kernel against fp64, entry by entry: tests/test_gpu_kmv_sums.py."""
     from example_problems.kinetic_mckean_vlasov_example_quadratic import KineticMcKeanVlasov
     from methods.consistency_instances import kinetic_mckean_vlasov as kmv
     from core.model import QuadraticModel
