@@ -1,7 +1,20 @@
-// realnvp.hip — time-conditioned RealNVP log-density (core/normalizing_flow.py:8-229).
-// One thread per (t, x) sample; all tiny MLPs (widths 8 / 16 / 16) run in
-// VGPRs on the VALU. The weights are read at wave-uniform addresses (scalar loads, one fetch
-// serves the 64 samples of a wave); masks and the base Gaussian travel in the kernel arguments.
+// realnvp.hip — the time-conditioned RealNVP flow (core/normalizing_flow.py:8-229) in three parts:
+//  1. realnvp_logdensity_kernel: log p_t(x), one thread per (t, x) sample, the tiny MLPs (widths 8 / 16 / 16,
+//     SURVEY.md §8(a) a12) in VGPRs on the VALU, weights at wave-uniform addresses (scalar loads). Helpers:
+//     nvp_act, dense, basic_mlp.
+//  2. realnvp_grad_kernel (+ nvp_slab_split_kernel, nvp_grad_reduce_kernel): value and parameter gradient of the
+//     maximum-likelihood loss on the matrix cores, 16-sample tiles. Helpers: the tile machinery nv_* (NvM / NvC /
+//     NvScr layouts, NvLane, nv_fwdT, nv_wgrad, nv_mlp_fwd / _bwd, nv_put_*, nv_layer_dst, nv_slab_col).
+//  3. The time derivatives (log p, d/dt, d2/dt2): realnvp_time_kernel (general, one thread per sample; helpers
+//     nvp_act_d2, nvp_act3, dense3_*, basic_mlp3) and realnvp_time_mfma_kernel (matrix cores; nv_fwdT3, nv_bias3,
+//     nv_celu3, nv_mlp_fwd3 on part 2's tile machinery).
+// Shared: NvpArgs (masks and the base Gaussian travel in the kernel arguments) and nvp_temb_params by all;
+// the block-level staging nv_lane / nv_stage_* by the two tile kernels; the three-stream arithmetic nvp_act3,
+// NVP_COUPLE3 and NVP_BASE_STORE3 (macros: see there) by the two time kernels; one descriptor
+// check (NVP_REQUIRE_DESC) and one NvpArgs fill (nvp_args) by the three host entry points.
+// Still written twice, on purpose: the time embedding's forward (sinusoid, bias, nv_fwdT, celu) in
+// realnvp_grad_kernel, once for the likelihood pass and once for the backward (see the comment at the second), and
+// the three lines of sample addressing (per-sample / sets view) in the two time kernels.
 #include <math.h>
 
 #include "common.h"
@@ -14,6 +27,9 @@ struct NvpArgs {
   float mean[8], inv_cov[64];
   float masks[PDEINV_REALNVP_MAX_LAYERS * 8];
 };
+
+// Parameters of the time embedding (two E x E dense layers), in front of the coupling layers; none for E = 0.
+__host__ __device__ constexpr int64_t nvp_temb_params(int E) { return E > 0 ? 2 * ((int64_t)E * E + E) : 0; }
 
 __device__ __forceinline__ float nvp_act(int act, float x) {
   switch (act) {
@@ -603,16 +619,86 @@ __device__ __forceinline__ uint32_t nv_layer_dst(int k, int d, int n_t) {
   return vec(NvM<PK>::B3, nv_xpos<PK>(f));
 }
 
-template <int ACT, bool PK>
+// ---- block-level staging of the two tile kernels (every thread of the block calls; barriers are the caller's) ----
+// with_stage: the lane's offsets into the per-wave sample stage (the gradient kernel's weight-gradient products)
+__device__ __forceinline__ NvLane nv_lane(int tid, bool with_stage) {
+  int lane = tid & 63;
+  asm volatile("" : "+v"(lane));  // opaque: keeps per-use address math out of long-lived registers
+  NvLane ln;
+  ln.g = lane >> 4;
+  ln.s = lane & 15;
+  ln.sw = with_stage ? ln.s * kNvSS + 4 * (ln.g ^ nv_swz(ln.s)) : 0;
+  ln.sr = with_stage ? ln.g * kNvSS + (ln.s ^ (4 * nv_swz(ln.g))) : 0;
+  return ln;
+}
+// padded [16][kNvWS] (and its transpose unless dst_t is null): position (r, c) <- src[rm(r)][cm(c)], 0 where a
+// map gives -1
+template <typename RM, typename CM>
+__device__ __forceinline__ void nv_stage_mat(float* dst, float* dst_t, const float* src, int ld_src, RM rm, CM cm) {
+  for (int q = threadIdx.x; q < 16 * kNvWS; q += kBlock) {
+    const int r = q / kNvWS, c = q - r * kNvWS;
+    const int sr = c < 16 ? rm(r) : -1, sc = c < 16 ? cm(c) : -1;
+    dst[q] = (sr >= 0 && sc >= 0) ? src[sr * ld_src + sc] : 0.f;
+    if (dst_t) {
+      const int tr = c < 16 ? rm(c) : -1, tc = c < 16 ? cm(r) : -1;
+      dst_t[q] = (tr >= 0 && tc >= 0) ? src[tr * ld_src + tc] : 0.f;
+    }
+  }
+}
+template <typename PM>
+__device__ __forceinline__ void nv_stage_vec(float* dst, const float* src, PM m) {
+  for (int q = threadIdx.x; q < 16; q += kBlock) {
+    const int k = m(q);
+    dst[q] = k >= 0 ? src[k] : 0.f;
+  }
+}
+// the time embedding's matrices into the start of the layer image sW, temb at its positions
+template <bool PK>
+__device__ __forceinline__ void nv_stage_temb(float* sW, const float* params, int E, bool with_transpose) {
+  using M = NvM<PK>;
+  auto idn = [E](int p) { return p < E ? p : -1; };
+  auto tmap = [E](int p) { return nv_tinv<PK>(p, E); };
+  nv_stage_mat(sW + M::E_W1, nullptr, params, E, idn, idn);
+  nv_stage_vec(sW + M::E_B1, params + E * E, idn);
+  nv_stage_mat(sW + M::E_W2, with_transpose ? sW + M::E_W2T : nullptr, params + E * E + E, E, idn, tmap);
+  nv_stage_vec(sW + M::E_B2, params + 2 * E * E + E, tmap);
+}
+// sinusoid table sF[48]: frequency freq(q), sin weight, cos weight of position q (all 0 for q >= E)
+template <typename FQ>
+__device__ __forceinline__ void nv_stage_sinusoid(float* sF, int E, FQ freq) {
+  const int tid = threadIdx.x;
+  if (tid < 16) {
+    const bool on = tid < E, is_sin = tid < E / 2;
+    sF[tid] = on ? freq(tid) : 0.f;
+    sF[16 + tid] = on && is_sin ? 1.f : 0.f;
+    sF[32 + tid] = on && !is_sin ? 1.f : 0.f;
+  }
+}
+// the nv_layer_dst table, and the layer image zeroed (its padding is never written again)
+template <bool PK>
+__device__ __forceinline__ void nv_stage_init(uint32_t* sDst, float* sW, int64_t layer_stride, int d, int n_t) {
+  for (int k = threadIdx.x; k < layer_stride; k += kBlock) sDst[k] = nv_layer_dst<PK>(k, d, n_t);
+  for (int q = threadIdx.x; q < NvM<PK>::LAYER; q += kBlock) sW[q] = 0.f;
+}
+// layer l's mask by position, padded with 1
+template <bool PK>
+__device__ __forceinline__ void nv_stage_mask(float* sW, const NvpArgs& a, int l, int d) {
+  const int tid = threadIdx.x;
+  if (tid < 16) {
+    const int k = nv_xinv<PK>(tid, d);
+    sW[NvM<PK>::MASK + tid] = k >= 0 ? a.masks[l * d + k] : 1.f;
+  }
+}
+
+template <bool PK>
 __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_grad_kernel(NvpArgs a, int d, const float* __restrict__ params,
                                                                  const float* __restrict__ tv, int64_t t_stride,
                                                                  const float* __restrict__ xv, int64_t n, int64_t ld,
                                                                  int64_t layer_stride, int64_t n_params,
                                                                  int64_t tile0, float* __restrict__ slab,
                                                                  int64_t slab_ld) {
-  static_assert(ACT == PDEINV_ACT_CELU, "celu / elu flow");
-  __shared__ float sW[NvM<PK>::LAYER];  // current coupling layer (padded); the time embedding before / after
-  float* const sT = sW;
+  // current coupling layer (padded); the time embedding's matrices at its start before the first / after the last
+  __shared__ float sW[NvM<PK>::LAYER];
   __shared__ float sF[48];              // sinusoid table: frequency, sin weight, cos weight
   __shared__ float sB[16 + 16 * 16];    // base mean, inverse covariance (0-padded)
   // per-wave sample stages and flush blocks (NvScr)
@@ -622,59 +708,19 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   const int E = a.E;
   const int n_in = a.in_dim, n_t = n_in - d;
   const int64_t lcb = (int64_t)a.n_layers * C::LAYER;  // slab-row offset of the time-embedding columns
-  const int64_t temb_params = E > 0 ? 2 * ((int64_t)E * E + E) : 0;
+  const int64_t temb_params = nvp_temb_params(E);
   const float* layers = params + temb_params;
   const bool hard = !a.ignore_time && a.soft_init == 0.f;
   const int tid = threadIdx.x, wave = tid >> 6;
-  NvLane ln;
-  {
-    int lane = tid & 63;
-    asm volatile("" : "+v"(lane));  // opaque: keeps per-use address math out of long-lived registers
-    ln.g = lane >> 4;
-    ln.s = lane & 15;
-    ln.sw = ln.s * kNvSS + 4 * (ln.g ^ nv_swz(ln.s));
-    ln.sr = ln.g * kNvSS + (ln.s ^ (4 * nv_swz(ln.g)));
-  }
-  float* stage = sScr[wave];
-  float* red = sScr[wave];
+  const NvLane ln = nv_lane(tid, true);
+  float* const scr = sScr[wave];  // the wave's sample stage, then its flush block (NvScr)
   // ---- per-block tables ----
-  // padded [16][kNvWS] (and its transpose): position (r, c) <- src[rm(r)][cm(c)], 0 where a map gives -1
-  auto put_mat = [&](float* dst, float* dst_t, const float* src, int ld_src, auto rm, auto cm) {
-    for (int q = tid; q < 16 * kNvWS; q += kBlock) {
-      const int r = q / kNvWS, c = q - r * kNvWS;
-      const int sr = c < 16 ? rm(r) : -1, sc = c < 16 ? cm(c) : -1;
-      dst[q] = (sr >= 0 && sc >= 0) ? src[sr * ld_src + sc] : 0.f;
-      if (dst_t) {
-        const int tr = c < 16 ? rm(c) : -1, tc = c < 16 ? cm(r) : -1;
-        dst_t[q] = (tr >= 0 && tc >= 0) ? src[tr * ld_src + tc] : 0.f;
-      }
-    }
-  };
-  auto put_vec = [&](float* dst, const float* src, auto m) {
-    for (int q = tid; q < 16; q += kBlock) {
-      const int k = m(q);
-      dst[q] = k >= 0 ? src[k] : 0.f;
-    }
-  };
-  auto idn = [](int len) { return [len](int p) { return p < len ? p : -1; }; };
-  auto put_temb = [&] {  // the time embedding's matrices into sT (= the start of sW)
-    auto tmap = [E](int p) { return nv_tinv<PK>(p, E); };
-    put_mat(sT + NvM<PK>::E_W1, nullptr, params, E, idn(E), idn(E));
-    put_vec(sT + NvM<PK>::E_B1, params + E * E, idn(E));
-    put_mat(sT + NvM<PK>::E_W2, sT + NvM<PK>::E_W2T, params + E * E + E, E, idn(E), tmap);  // temb at its positions
-    put_vec(sT + NvM<PK>::E_B2, params + 2 * E * E + E, tmap);
-  };
-  if (tid < 16) {
+  nv_stage_sinusoid(sF, E, [E](int q) {  // fp32 on the device (the time kernels: NvFreq)
     const int half = E / 2;
-    const bool on = E > 0 && tid < E;
-    const bool is_sin = tid < half;
-    const float step = E > 0 ? logf(10000.f) / (float)(half - 1) : 0.f;
-    sF[tid] = on ? expf(-step * (float)(is_sin ? tid : tid - half)) : 0.f;
-    sF[16 + tid] = on && is_sin ? 1.f : 0.f;
-    sF[32 + tid] = on && !is_sin ? 1.f : 0.f;
-  }
-  for (int k = tid; k < layer_stride; k += kBlock) sDst[k] = nv_layer_dst<PK>(k, d, n_t);
-  for (int q = tid; q < NvM<PK>::LAYER; q += kBlock) sW[q] = 0.f;  // padding: never written again
+    const float step = logf(10000.f) / (float)(half - 1);
+    return expf(-step * (float)(q < half ? q : q - half));
+  });
+  nv_stage_init<PK>(sDst, sW, layer_stride, d, n_t);
   for (int q = tid; q < 16 + 256; q += kBlock) {  // mean at the x positions; inv_cov rows by position, columns by coordinate
     float v = 0.f;
     if (q < 16) {
@@ -701,10 +747,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   int staged = 0;  // layers staged so far
   auto stage_layer = [&](int l) {
     __syncthreads();  // every wave is done with the previous layer
-    if (tid < 16) {  // the layer's mask by position, padded with 1
-      const int k = nv_xinv<PK>(tid, d);
-      sW[NvM<PK>::MASK + tid] = k >= 0 ? a.masks[l * d + k] : 1.f;
-    }
+    nv_stage_mask<PK>(sW, a, l, d);
 #pragma unroll
     for (int k = 0; k < kNvPre; ++k) {
       const int q = tid + k * kBlock;
@@ -737,7 +780,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   float tt[kNvT], w[kNvT], ldj[kNvT];
   const int64_t base = (tile0 + blockIdx.x) * kNvSPB + wave * 16 * kNvT;
   __syncthreads();  // sW zeroed
-  if (E > 0) put_temb();
+  if (E > 0) nv_stage_temb<PK>(sW, params, E, true);
   __syncthreads();
 #pragma unroll
   for (int u = 0; u < kNvT; ++u) {
@@ -764,15 +807,32 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
         se[u][c] = sF[16 + q] * sinf(e) + sF[32 + q] * cosf(e);
       }
   };
+  // Packed layout: the coordinates live in register 0 only (registers 1..3 of x, gx stay exactly 0 through
+  // every coupling layer), so the per-coordinate coupling math runs over NC = 1 register.
+  constexpr int NC = PK ? 1 : 4;
+  // sf = e^alpha and 1 / sf of the staged layer; the masked input of its nets (x a parameter, not a capture:
+  // captured, it costs the identity-layout kernel 12 bytes of scratch)
+  auto scale = [&](f32x4& sf, f32x4& isf) {
+    const f32x4 sfw = nv_vec(sW + NvM<PK>::SF, ln);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      sf[c] = nv_exp(sfw[c]);
+      isf[c] = __builtin_amdgcn_rcpf(sf[c]);
+    }
+  };
+  auto masked = [](const NvV& x, const f32x4& m, NvV& xm) {
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
+  };
   if (E > 0) {
     NvV se, he;
     sinusoid(se);
-    nv_bcast(he, nv_vec(sT + NvM<PK>::E_B1, ln));
-    nv_fwdT(sT + NvM<PK>::E_W1, ln, se, he);
+    nv_bcast(he, nv_vec(sW + NvM<PK>::E_B1, ln));
+    nv_fwdT(sW + NvM<PK>::E_W1, ln, se, he);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
-    nv_bcast(temb, nv_vec(sT + NvM<PK>::E_B2, ln));
-    nv_fwdT(sT + NvM<PK>::E_W2, ln, he, temb);
+    nv_bcast(temb, nv_vec(sW + NvM<PK>::E_B2, ln));
+    nv_fwdT(sW + NvM<PK>::E_W2, ln, he, temb);
     __syncthreads();  // every wave has read the time embedding: back to the zero-padded layer image
     for (int q = tid; q < NvM<PK>::TEMB; q += kBlock) sW[q] = 0.f;
   } else {
@@ -781,22 +841,14 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
 #pragma unroll
       for (int c = 0; c < 4; ++c) temb[u][c] = (!a.ignore_time && 4 * ln.g + c == nv_tpos<PK>(0)) ? tt[u] : 0.f;
   }
-  // Packed layout: the coordinates live in register 0 only (registers 1..3 of x, gx stay exactly 0 through
-  // every coupling layer), so the per-coordinate coupling math runs over NC = 1 register.
-  constexpr int NC = PK ? 1 : 4;
   // ---- likelihood pass (layers L-1 .. 0): x <- (x + tr) e^s ----
   for (int l = a.n_layers - 1; l >= 0; --l) {
     stage_layer(l);
-    const f32x4 m = nv_vec(sW + NvM<PK>::MASK, ln), sfw = nv_vec(sW + NvM<PK>::SF, ln);
+    const f32x4 m = nv_vec(sW + NvM<PK>::MASK, ln);
     f32x4 sf, isf;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      sf[c] = nv_exp(sfw[c]);
-      isf[c] = __builtin_amdgcn_rcpf(sf[c]);
-    }
+    scale(sf, isf);
     NvV xm, so, to;
-#pragma unroll
-    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
+    masked(x, m, xm);
     {
       NvAct h;
       nv_mlp_fwd<PK>(sW + NvM<PK>::SNET, ln, temb, xm, h, so);
@@ -819,7 +871,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   for (int u = 0; u < kNvT; ++u) {
     const f32x4 diff = x[u] - nv_vec(sB, ln);
     nv_wave_sync();
-    *reinterpret_cast<f32x4*>(stage + ln.sw) = diff;
+    *reinterpret_cast<f32x4*>(scr + ln.sw) = diff;
     nv_wave_sync();
     float quad = 0.f;
 #pragma unroll
@@ -827,7 +879,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
       const int r = 4 * ln.g + c;
       float acc = 0.f;
       for (int q = 0; q < d; ++q)
-        acc = fmaf(sB[16 + r * 16 + q], stage[ln.s * kNvSS + (nv_xpos<PK>(q) ^ (4 * nv_swz(ln.s)))], acc);
+        acc = fmaf(sB[16 + r * 16 + q], scr[ln.s * kNvSS + (nv_xpos<PK>(q) ^ (4 * nv_swz(ln.s)))], acc);
       quad = fmaf(diff[c], acc, quad);
       gx[u][c] = PK && c > 0 ? 0.f : -w[u] * acc;
     }
@@ -839,21 +891,16 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   // ---- backward through layers 0 .. L-1, rebuilding each layer's input ----
   for (int l = 0; l < a.n_layers; ++l) {
     stage_layer(l);
-    const f32x4 m = nv_vec(sW + NvM<PK>::MASK, ln), sfw = nv_vec(sW + NvM<PK>::SF, ln);
+    const f32x4 m = nv_vec(sW + NvM<PK>::MASK, ln);
     f32x4 sfv, isf;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      sfv[c] = nv_exp(sfw[c]);
-      isf[c] = __builtin_amdgcn_rcpf(sfv[c]);
-    }
+    scale(sfv, isf);
     NvNetAcc as, at;
     as.zero();
     at.zero();
     f32x4 galpha = {0.f, 0.f, 0.f, 0.f};
     NvV xm, out, s, es, gso, gto, gacc;
     NvAct h;
-#pragma unroll
-    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
+    masked(x, m, xm);
     nv_mlp_fwd<PK>(sW + NvM<PK>::SNET, ln, temb, xm, h, out);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u) {
@@ -873,11 +920,11 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
         gto[u][c] = (hard ? tt[u] : 1.f) * gx[u][c] * es[u][c] * keep;  // d/d translate_net output
       }
     }
-    nv_mlp_bwd<PK>(sW + NvM<PK>::SNET, ln, stage, temb, xm, h, gso, as, gtemb, gacc);
-    nv_put_vec(red + NvScr<PK>::TR + NvC<PK>::NET, ln, galpha);  // behind the stage (nv_flush_lds)
-    nv_put_net<PK>(red + NvScr<PK>::TR, ln, as);
+    nv_mlp_bwd<PK>(sW + NvM<PK>::SNET, ln, scr, temb, xm, h, gso, as, gtemb, gacc);
+    nv_put_vec(scr + NvScr<PK>::TR + NvC<PK>::NET, ln, galpha);  // behind the stage (nv_flush_lds)
+    nv_put_net<PK>(scr + NvScr<PK>::TR, ln, as);
     nv_mlp_fwd<PK>(sW + NvM<PK>::TNET, ln, temb, xm, h, out);
-    nv_mlp_bwd<PK>(sW + NvM<PK>::TNET, ln, stage, temb, xm, h, gto, at, gtemb, gacc);
+    nv_mlp_bwd<PK>(sW + NvM<PK>::TNET, ln, scr, temb, xm, h, gto, at, gtemb, gacc);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u)
 #pragma unroll
@@ -890,7 +937,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
     // the block's four wave blocks summed as float4 into the layer's slab-row segment. The next stage_layer's
     // barrier orders these reads before any wave's next stage writes.
     nv_wave_sync();
-    nv_put_net<PK>(red + C::TNET, ln, at);
+    nv_put_net<PK>(scr + C::TNET, ln, at);
     __syncthreads();
     for (int q = tid; q < C::LAYER / 4; q += kBlock) {
       const int o = nv_flush_lds<PK>(4 * q);
@@ -902,33 +949,35 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   }
   __syncthreads();  // the last layer's sums are read: the stages and the layer image are free again
   if (E > 0) {
-    put_temb();
+    nv_stage_temb<PK>(sW, params, E, true);
     __syncthreads();
   }
   // ---- time-embedding backward and the loss column ----
   if (E > 0) {
     f32x4 w1 = {0.f, 0.f, 0.f, 0.f}, w2 = w1, b1 = w1, b2 = w1;
     NvV se, he, gz;
+    // se and he again (the forward kept neither). Sinusoid and hidden layer stay two steps written out at both
+    // places: as one local, lambda or function, they cost the packed kernel 3 more spilled dwords (168 VGPRs).
     sinusoid(se);
-    nv_bcast(he, nv_vec(sT + NvM<PK>::E_B1, ln));
-    nv_fwdT(sT + NvM<PK>::E_W1, ln, se, he);
+    nv_bcast(he, nv_vec(sW + NvM<PK>::E_B1, ln));
+    nv_fwdT(sW + NvM<PK>::E_W1, ln, se, he);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
-    w2 = nv_wgrad(stage, ln, he, gtemb, w2);
+    w2 = nv_wgrad(scr, ln, he, gtemb, w2);
     nv_bcast(gz, f32x4{0.f, 0.f, 0.f, 0.f});
-    nv_fwdT(sT + NvM<PK>::E_W2T, ln, gtemb, gz);
+    nv_fwdT(sW + NvM<PK>::E_W2T, ln, gtemb, gz);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u) {
       b2 += gtemb[u];
       gz[u] = nv_dact4(gz[u], he[u]);
       b1 += gz[u];
     }
-    w1 = nv_wgrad(stage, ln, se, gz, w1);
+    w1 = nv_wgrad(scr, ln, se, gz, w1);
     __syncthreads();  // stages done (flush blocks alias them)
-    nv_put_mat(red + 0, ln, w1);
-    nv_put_vec(red + 256, ln, b1);
-    nv_put_mat(red + 272, ln, w2);
-    nv_put_vec(red + 528, ln, b2);
+    nv_put_mat(scr + 0, ln, w1);
+    nv_put_vec(scr + 256, ln, b1);
+    nv_put_mat(scr + 272, ln, w2);
+    nv_put_vec(scr + 528, ln, b2);
     const int EE = E * E + E;
     flush(lcb, 2 * EE, [&](int f) {
       const int part = f >= EE, r = f - part * EE;
@@ -941,7 +990,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   lsum += __shfl_xor(lsum, 2, 64);
   lsum += __shfl_xor(lsum, 4, 64);
   lsum += __shfl_xor(lsum, 8, 64);
-  if (tid % 64 == 0) red[0] = lsum;
+  if (tid % 64 == 0) scr[0] = lsum;
   flush(lcb + temb_params, 1, [&](int) { return 0; });
 }
 
@@ -1061,6 +1110,16 @@ __device__ __forceinline__ void nvp_act_d2(float z, float& g, float& g1, float& 
   }
 }
 
+// y = g(z) on the three streams, in place: y' = g' z', y'' = g'' z'^2 + g' z''
+template <int ACT>
+__device__ __forceinline__ void nvp_act3(float& z0, float& z1, float& z2) {
+  float g, g1, g2;
+  nvp_act_d2<ACT>(z0, g, g1, g2);
+  z0 = g;
+  z2 = fmaf(g2 * z1, z1, g1 * z2);
+  z1 = g1 * z1;
+}
+
 // The three streams of a dense layer out = act?(b + in @ W) in pieces: bias (value stream only), the rows of one
 // input block (rows i >= n_in of the NI-wide block are not read; one weight fetch feeds three FMAs), activation.
 template <int NO>
@@ -1092,14 +1151,7 @@ __device__ __forceinline__ void dense3_rows(const float* __restrict__ W, const f
 template <int ACT, int NO>
 __device__ __forceinline__ void dense3_act(float (&out)[3][NO]) {
 #pragma unroll
-  for (int o = 0; o < NO; ++o) {
-    float g, g1, g2;
-    nvp_act_d2<ACT>(out[0][o], g, g1, g2);
-    const float z1 = out[1][o];
-    out[0][o] = g;
-    out[2][o] = fmaf(g2 * z1, z1, g1 * out[2][o]);
-    out[1][o] = g1 * z1;
-  }
+  for (int o = 0; o < NO; ++o) nvp_act3<ACT>(out[0][o], out[1][o], out[2][o]);
 }
 
 // BasicMLP over the input [xm (D) | temb (n_t)] kept as its two blocks
@@ -1132,6 +1184,75 @@ __device__ __forceinline__ const float* basic_mlp3(const float* p, const float (
 struct NvFreq {
   float w[16];
 };
+
+// The two formulas that both time kernels must evaluate alike, each defined once. They are statement macros, not
+// functions: called from realnvp_time_kernel as __forceinline__ functions (array, scalar-reference, by-value and
+// restrict-free signatures were tried) the same text changes that kernel's instruction stream, with the same
+// resource table but more SGPR spills, and costs it 0.5 - 1 % (d = 4, 7, 8); expanded in place both kernels
+// compile to the instructions they had. Arguments are evaluated more than once (pass plain variables or array
+// elements); the macros' own names end in _ so that they capture none of the caller's.
+//
+// NVP_COUPLE3: the coupling update of one coordinate of one sample on the three streams: x <- (x + tr keep) e^{sk},
+// sk = tanh(s / sf) sf keep, ldj += sk, with s and tr the nets' outputs (times t under the hard parameterisation).
+// On the accurate expf / tanhf / division (d per layer, against the nets' hundreds of activations): the three
+// streams of x are large and every later layer sees their rounding, so an ulp here is what the derivatives' error
+// is made of. S*, T*: the nets' outputs (values); X*, L*: the streams of x and ldj (lvalues).
+#define NVP_COUPLE3(t, hard, sf, keep, S0, S1, S2, T0, T1, T2, X0, X1, X2, L0, L1, L2)             \
+  do {                                                                                            \
+    float s0_ = (S0), s1_ = (S1), s2_ = (S2);                                                     \
+    float t0_ = (T0), t1_ = (T1), t2_ = (T2);                                                     \
+    if (hard) { /* (t f)' = f + t f', (t f)'' = 2 f' + t f'' */                                   \
+      s2_ = fmaf((t), s2_, 2.f * s1_);                                                            \
+      s1_ = fmaf((t), s1_, s0_);                                                                  \
+      s0_ *= (t);                                                                                 \
+      t2_ = fmaf((t), t2_, 2.f * t1_);                                                            \
+      t1_ = fmaf((t), t1_, t0_);                                                                  \
+      t0_ *= (t);                                                                                 \
+    }                                                                                             \
+    const float sf_ = (sf);                                                                       \
+    const float th_ = tanhf(s0_ / sf_), g1_ = 1.f - th_ * th_;                                    \
+    const float k0_ = th_ * sf_ * (keep);                                                         \
+    const float k1_ = g1_ * s1_ * (keep);                                                         \
+    const float k2_ = g1_ * (s2_ - 2.f * th_ * s1_ * s1_ / sf_) * (keep);                         \
+    const float e0_ = expf(k0_), e1_ = e0_ * k1_, e2_ = e0_ * fmaf(k1_, k1_, k2_);                \
+    const float y0_ = (X0) + t0_ * (keep), y1_ = (X1) + t1_ * (keep), y2_ = (X2) + t2_ * (keep);  \
+    (X0) = y0_ * e0_;                                                                             \
+    (X1) = fmaf(y1_, e0_, y0_ * e1_);                                                             \
+    (X2) = fmaf(y2_, e0_, fmaf(2.f * y1_, e1_, y0_ * e2_));                                       \
+    (L0) += k0_;                                                                                  \
+    (L1) += k1_;                                                                                  \
+    (L2) += k2_;                                                                                  \
+  } while (0)
+
+// NVP_BASE_STORE3: base density and the outputs of sample i: quad = diff^T A diff and its derivatives (A need not be
+// symmetric) over the first d of the DMAX coordinates in x[3][DMAX], then (log p, d/dt, d2/dt2) =
+// (-0.5 (log_det + q0) + ldj0, -0.5 q1 + ldj1, -0.5 q2 + ldj2); ignore_time writes exact zeros for the derivatives.
+// The general path passes DMAX = d = D, the matrix-core path DMAX = 4 and its runtime d.
+#define NVP_BASE_STORE3(a, x, DMAX, d, ldj, i, logp, ds)                                         \
+  do {                                                                                           \
+    float q0_ = 0.f, q1_ = 0.f, q2_ = 0.f;                                                       \
+    _Pragma("unroll") for (int r_ = 0; r_ < (DMAX); ++r_) {                                      \
+      if (r_ < (d)) {                                                                            \
+        float a0_ = 0.f, a1_ = 0.f, a2_ = 0.f;                                                   \
+        _Pragma("unroll") for (int c_ = 0; c_ < (DMAX); ++c_) {                                  \
+          if (c_ < (d)) {                                                                        \
+            const float w_ = (a).inv_cov[r_ * (d) + c_];                                         \
+            a0_ = fmaf(w_, (x)[0][c_] - (a).mean[c_], a0_);                                      \
+            a1_ = fmaf(w_, (x)[1][c_], a1_);                                                     \
+            a2_ = fmaf(w_, (x)[2][c_], a2_);                                                     \
+          }                                                                                      \
+        }                                                                                        \
+        const float d0_ = (x)[0][r_] - (a).mean[r_];                                             \
+        q0_ = fmaf(d0_, a0_, q0_);                                                               \
+        q1_ = fmaf((x)[1][r_], a0_, fmaf(d0_, a1_, q1_));                                        \
+        q2_ = fmaf((x)[2][r_], a0_, fmaf(2.f * (x)[1][r_], a1_, fmaf(d0_, a2_, q2_)));           \
+      }                                                                                          \
+    }                                                                                            \
+    if (logp) (logp)[i] = -0.5f * ((a).log_det + q0_) + (ldj)[0];                                \
+    f32x2 o_ = {fmaf(-0.5f, q1_, (ldj)[1]), fmaf(-0.5f, q2_, (ldj)[2])};                         \
+    if ((a).ignore_time) o_ = f32x2{0.f, 0.f};                                                   \
+    *reinterpret_cast<f32x2*>((ds) + 2 * (i)) = o_;                                              \
+  } while (0)
 
 // Sample i: n_rows == 0: (tv[i * t_stride], xv + i * ld); n_rows > 0 (the sets view of pdeinv_kmv_weights):
 // set = i / n_rows, row r = i % n_rows: (tv[set], xv + set * set_stride + r * ld). Outputs at index i.
@@ -1176,7 +1297,9 @@ __global__ __launch_bounds__(kBlock, 2) void realnvp_time_kernel(NvpArgs a, NvFr
           se[2][q] = -w * w * se[0][q];
         }
       }
-      // two E x E dense layers; unrolled to 16 x 16 with the rows and columns >= E skipped
+      // two E x E dense layers; unrolled to 16 x 16 with the rows and columns >= E skipped. (A local, not dense3_bias /
+      // dense3_rows given a runtime stride and width: that form changes the register allocation of this kernel, whose
+      // instruction stream is kept as it was.)
       auto layer = [&](const float* W, const float (&in)[3][16], float (&out)[3][16]) {
 #pragma unroll
         for (int o = 0; o < 16; ++o) {
@@ -1201,16 +1324,8 @@ __global__ __launch_bounds__(kBlock, 2) void realnvp_time_kernel(NvpArgs a, NvFr
       };
       layer(p, se, h);
 #pragma unroll
-      for (int o = 0; o < 16; ++o) {
-        if (o < E) {
-          float g, g1, g2;
-          nvp_act_d2<ACT>(h[0][o], g, g1, g2);
-          const float z1 = h[1][o];
-          h[0][o] = g;
-          h[2][o] = fmaf(g2 * z1, z1, g1 * h[2][o]);
-          h[1][o] = g1 * z1;
-        }
-      }
+      for (int o = 0; o < 16; ++o)
+        if (o < E) nvp_act3<ACT>(h[0][o], h[1][o], h[2][o]);
       p += E * E + E;
       layer(p, h, temb);
       p += E * E + E;
@@ -1238,56 +1353,11 @@ __global__ __launch_bounds__(kBlock, 2) void realnvp_time_kernel(NvpArgs a, NvFr
 #pragma unroll
     for (int k = 0; k < D; ++k) {
       const float keep = 1.f - m[k];
-      float s0 = sc[0][k], s1 = sc[1][k], s2 = sc[2][k];
-      float t0 = tr[0][k], t1 = tr[1][k], t2 = tr[2][k];
-      if (hard) {  // (t f)' = f + t f', (t f)'' = 2 f' + t f''
-        s2 = fmaf(t, s2, 2.f * s1);
-        s1 = fmaf(t, s1, s0);
-        s0 *= t;
-        t2 = fmaf(t, t2, 2.f * t1);
-        t1 = fmaf(t, t1, t0);
-        t0 *= t;
-      }
-      // The coupling update itself on the accurate expf / tanhf / division (d per layer, against the nets' hundreds
-      // of activations): the three streams of x are large and every later layer sees their rounding, so an ulp
-      // here is what the derivatives' error is made of.
-      const float sf = expf(sfp[k]);
-      const float th = tanhf(s0 / sf), g1 = 1.f - th * th;
-      // sk = tanh(s / sf) sf keep
-      const float k0 = th * sf * keep;
-      const float k1 = g1 * s1 * keep;
-      const float k2 = g1 * (s2 - 2.f * th * s1 * s1 / sf) * keep;
-      const float e0 = expf(k0), e1 = e0 * k1, e2 = e0 * fmaf(k1, k1, k2);
-      const float y0 = x[0][k] + t0 * keep, y1 = x[1][k] + t1 * keep, y2 = x[2][k] + t2 * keep;
-      x[0][k] = y0 * e0;
-      x[1][k] = fmaf(y1, e0, y0 * e1);
-      x[2][k] = fmaf(y2, e0, fmaf(2.f * y1, e1, y0 * e2));
-      ldj[0] += k0;
-      ldj[1] += k1;
-      ldj[2] += k2;
+      NVP_COUPLE3(t, hard, expf(sfp[k]), keep, sc[0][k], sc[1][k], sc[2][k], tr[0][k], tr[1][k], tr[2][k], x[0][k], x[1][k],
+                  x[2][k], ldj[0], ldj[1], ldj[2]);
     }
   }
-  // quad = diff^T A diff and its derivatives (A need not be symmetric)
-  float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-#pragma unroll
-  for (int r = 0; r < D; ++r) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-      const float w = a.inv_cov[r * D + c];
-      a0 = fmaf(w, x[0][c] - a.mean[c], a0);
-      a1 = fmaf(w, x[1][c], a1);
-      a2 = fmaf(w, x[2][c], a2);
-    }
-    const float d0 = x[0][r] - a.mean[r];
-    q0 = fmaf(d0, a0, q0);
-    q1 = fmaf(x[1][r], a0, fmaf(d0, a1, q1));
-    q2 = fmaf(x[2][r], a0, fmaf(2.f * x[1][r], a1, fmaf(d0, a2, q2)));
-  }
-  if (logp) logp[i] = -0.5f * (a.log_det + q0) + ldj[0];
-  f32x2 o = {fmaf(-0.5f, q1, ldj[1]), fmaf(-0.5f, q2, ldj[2])};
-  if (a.ignore_time) o = f32x2{0.f, 0.f};
-  *reinterpret_cast<f32x2*>(ds + 2 * i) = o;
+  NVP_BASE_STORE3(a, x, D, D, ldj, i, logp, ds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1325,12 +1395,11 @@ __device__ __forceinline__ void nv_celu3(NvV3& z) {
   for (int u = 0; u < kNvT; ++u)
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      float g, g1, g2;
-      nvp_act_d2<PDEINV_ACT_CELU>(z[0][u][c], g, g1, g2);
-      const float z1 = z[1][u][c];
-      z[0][u][c] = g;
-      z[2][u][c] = fmaf(g2 * z1, z1, g1 * z[2][u][c]);
-      z[1][u][c] = g1 * z1;
+      float v0 = z[0][u][c], v1 = z[1][u][c], v2 = z[2][u][c];  // (a vector's element binds to no reference)
+      nvp_act3<PDEINV_ACT_CELU>(v0, v1, v2);
+      z[0][u][c] = v0;
+      z[1][u][c] = v1;
+      z[2][u][c] = v2;
     }
 }
 // BasicMLP on the three streams, packed layout: input [xm (register 0) | temb (registers 1..3)]
@@ -1365,45 +1434,14 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
   __shared__ float sF[48];        // sinusoid table: frequency, sin weight, cos weight
   __shared__ uint32_t sDst[kNvRaw];
   const int E = a.E, n_t = a.in_dim - d;
-  const float* layers = params + 2 * ((int64_t)E * E + E);
+  const float* layers = params + nvp_temb_params(E);
   const bool hard = a.soft_init == 0.f;
   const int tid = threadIdx.x, wave = tid >> 6;
-  NvLane ln;
-  {
-    int lane = tid & 63;
-    asm volatile("" : "+v"(lane));
-    ln.g = lane >> 4;
-    ln.s = lane & 15;
-    ln.sw = ln.sr = 0;
-  }
-  auto put_mat = [&](float* dst, const float* src, int ld_src, auto rm, auto cm) {
-    for (int q = tid; q < 16 * kNvWS; q += kBlock) {
-      const int r = q / kNvWS, c = q - r * kNvWS;
-      const int sr = c < 16 ? rm(r) : -1, sc = c < 16 ? cm(c) : -1;
-      dst[q] = (sr >= 0 && sc >= 0) ? src[sr * ld_src + sc] : 0.f;
-    }
-  };
-  auto put_vec = [&](float* dst, const float* src, auto m) {
-    for (int q = tid; q < 16; q += kBlock) {
-      const int k = m(q);
-      dst[q] = k >= 0 ? src[k] : 0.f;
-    }
-  };
-  auto idn = [E](int p) { return p < E ? p : -1; };
-  auto tmap = [E](int p) { return nv_tinv<true>(p, E); };
-  if (tid < 16) {
-    const bool on = tid < E, is_sin = tid < E / 2;
-    sF[tid] = on ? fr.w[tid] : 0.f;
-    sF[16 + tid] = on && is_sin ? 1.f : 0.f;
-    sF[32 + tid] = on && !is_sin ? 1.f : 0.f;
-  }
-  for (int k = tid; k < layer_stride; k += kBlock) sDst[k] = nv_layer_dst<true>(k, d, n_t);
-  for (int q = tid; q < M::LAYER; q += kBlock) sW[q] = 0.f;  // padding: never written by a layer
+  const NvLane ln = nv_lane(tid, false);
+  nv_stage_sinusoid(sF, E, [&fr](int q) { return fr.w[q]; });  // rounded from fp64 on the host (NvFreq)
+  nv_stage_init<true>(sDst, sW, layer_stride, d, n_t);
   __syncthreads();
-  put_mat(sW + M::E_W1, params, E, idn, idn);
-  put_vec(sW + M::E_B1, params + E * E, idn);
-  put_mat(sW + M::E_W2, params + E * E + E, E, idn, tmap);  // temb at its positions
-  put_vec(sW + M::E_B2, params + 2 * E * E + E, tmap);
+  nv_stage_temb<true>(sW, params, E, false);
   __syncthreads();
   // ---- the wave's tiles: lane (g, s) holds coordinate g of sample s ----
   float xs[3][kNvT], tt[kNvT], ldj[3][kNvT];
@@ -1453,10 +1491,7 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
     __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
     const float* lp = layers + (int64_t)l * layer_stride;
     for (int k = tid; k < layer_stride; k += kBlock) sW[sDst[k] & 0xFFFFu] = lp[k];
-    if (tid < 16) {  // the layer's mask by position, padded with 1
-      const int k = nv_xinv<true>(tid, d);
-      sW[M::MASK + tid] = k >= 0 ? a.masks[l * d + k] : 1.f;
-    }
+    nv_stage_mask<true>(sW, a, l, d);
     __syncthreads();
     const float m = sW[M::MASK + 4 * ln.g], keep = 1.f - m;
     const float sf = expf(sW[M::SF + 4 * ln.g]);
@@ -1469,31 +1504,9 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
     nv_mlp_fwd3(sW + M::SNET, ln, temb, xm, so);
     nv_mlp_fwd3(sW + M::TNET, ln, temb, xm, to);
 #pragma unroll
-    for (int u = 0; u < kNvT; ++u) {
-      const float t = tt[u];
-      float s0 = so[0][u][0], s1 = so[1][u][0], s2 = so[2][u][0];
-      float t0 = to[0][u][0], t1 = to[1][u][0], t2 = to[2][u][0];
-      if (hard) {
-        s2 = fmaf(t, s2, 2.f * s1);
-        s1 = fmaf(t, s1, s0);
-        s0 *= t;
-        t2 = fmaf(t, t2, 2.f * t1);
-        t1 = fmaf(t, t1, t0);
-        t0 *= t;
-      }
-      const float th = tanhf(s0 / sf), g1 = 1.f - th * th;
-      const float k0 = th * sf * keep;
-      const float k1 = g1 * s1 * keep;
-      const float k2 = g1 * (s2 - 2.f * th * s1 * s1 / sf) * keep;
-      const float e0 = expf(k0), e1 = e0 * k1, e2 = e0 * fmaf(k1, k1, k2);
-      const float y0 = xs[0][u] + t0 * keep, y1 = xs[1][u] + t1 * keep, y2 = xs[2][u] + t2 * keep;
-      xs[0][u] = y0 * e0;
-      xs[1][u] = fmaf(y1, e0, y0 * e1);
-      xs[2][u] = fmaf(y2, e0, fmaf(2.f * y1, e1, y0 * e2));
-      ldj[0][u] += k0;
-      ldj[1][u] += k1;
-      ldj[2][u] += k2;
-    }
+    for (int u = 0; u < kNvT; ++u)  // register 0: the lane group's coordinate
+      NVP_COUPLE3(tt[u], hard, sf, keep, so[0][u][0], so[1][u][0], so[2][u][0], to[0][u][0], to[1][u][0], to[2][u][0],
+                  xs[0][u], xs[1][u], xs[2][u], ldj[0][u], ldj[1][u], ldj[2][u]);
   }
   // ---- base density: every lane gathers its sample's coordinates (lane 16 c + s holds coordinate c) ----
 #pragma unroll
@@ -1508,31 +1521,7 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
       v += __shfl_xor(v, 32, 64);
       lj[s] = v;
     }
-    float q0 = 0.f, q1 = 0.f, q2 = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (r < d) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          if (c < d) {
-            const float w = a.inv_cov[r * d + c];
-            a0 = fmaf(w, xc[0][c] - a.mean[c], a0);
-            a1 = fmaf(w, xc[1][c], a1);
-            a2 = fmaf(w, xc[2][c], a2);
-          }
-        }
-        const float d0 = xc[0][r] - a.mean[r];
-        q0 = fmaf(d0, a0, q0);
-        q1 = fmaf(xc[1][r], a0, fmaf(d0, a1, q1));
-        q2 = fmaf(xc[2][r], a0, fmaf(2.f * xc[1][r], a1, fmaf(d0, a2, q2)));
-      }
-    }
-    const int64_t i = idx[u];
-    if (ln.g == 0 && i >= 0) {
-      if (logp) logp[i] = -0.5f * (a.log_det + q0) + lj[0];
-      *reinterpret_cast<f32x2*>(ds + 2 * i) = f32x2{fmaf(-0.5f, q1, lj[1]), fmaf(-0.5f, q2, lj[2])};
-    }
+    if (ln.g == 0 && idx[u] >= 0) NVP_BASE_STORE3(a, xc, 4, d, lj, idx[u], logp, ds);
   }
 }
 
@@ -1545,32 +1534,26 @@ static int in_dim_of(const pdeinv_realnvp_desc* d) {
   return d->ignore_time ? d->dim : d->dim + (d->embed_time_dim > 0 ? d->embed_time_dim : 1);
 }
 
-}  // namespace pdeinv
+// The descriptor checks of every entry point, in one fixed order; who is the entry point's message prefix (a
+// literal: no string is built unless a check fails). The trailing arguments, if any, are the entry point's own
+// requirement on the descriptor, checked where it always was: after the activation's range, before the host arrays.
+// It is passed as one whole PDEINV_REQUIRE(...) statement: commas inside its parentheses are safe, a comma outside
+// any parentheses would split it. Without it the expansion holds one empty statement.
+#define NVP_REQUIRE_DESC(d, who, ...)                                                                              \
+  PDEINV_REQUIRE((d) != nullptr, PDEINV_ERR_INVALID, who ": null descriptor");                                     \
+  PDEINV_REQUIRE((d)->dim >= 1 && (d)->dim <= 8, PDEINV_ERR_UNSUPPORTED, who ": dim must be in [1, 8]");           \
+  PDEINV_REQUIRE((d)->n_layers >= 1 && (d)->n_layers <= PDEINV_REALNVP_MAX_LAYERS, PDEINV_ERR_UNSUPPORTED,         \
+                 who ": 1 <= n_layers <= 64");                                                                     \
+  PDEINV_REQUIRE((d)->embed_time_dim >= 0 && (d)->embed_time_dim <= 16 && (d)->embed_time_dim % 2 == 0 &&          \
+                     (d)->embed_time_dim != 2,                                                                     \
+                 PDEINV_ERR_UNSUPPORTED, who ": embed_time_dim must be 0 or even in [4, 16]");                     \
+  PDEINV_REQUIRE((d)->activation >= PDEINV_ACT_CELU && (d)->activation <= PDEINV_ACT_GELU, PDEINV_ERR_UNSUPPORTED, \
+                 who ": unknown activation");                                                                      \
+  __VA_ARGS__;                                                                                                     \
+  PDEINV_REQUIRE((d)->masks && (d)->base_mean && (d)->base_inv_cov, PDEINV_ERR_INVALID, who ": null host array")
 
-using namespace pdeinv;
-
-extern "C" int64_t pdeinv_realnvp_param_count(const pdeinv_realnvp_desc* d) {
-  if (!d || d->dim < 1 || d->dim > 8 || d->n_layers < 1 || d->embed_time_dim < 0) return -1;
-  const int E = d->ignore_time ? 0 : d->embed_time_dim;
-  return (E > 0 ? 2 * ((int64_t)E * E + E) : 0) + (int64_t)d->n_layers * layer_params(d->dim, in_dim_of(d));
-}
-
-extern "C" int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* d, const float* params, const float* t,
-                                         int64_t t_stride, const float* x, int64_t n, int64_t ld, float* out,
-                                         void* stream) {
-  PDEINV_REQUIRE(d != nullptr, PDEINV_ERR_INVALID, "realnvp: null descriptor");
-  PDEINV_REQUIRE(d->dim >= 1 && d->dim <= 8, PDEINV_ERR_UNSUPPORTED, "realnvp: dim must be in [1, 8]");
-  PDEINV_REQUIRE(d->n_layers >= 1 && d->n_layers <= PDEINV_REALNVP_MAX_LAYERS, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp: 1 <= n_layers <= 64");
-  PDEINV_REQUIRE(d->embed_time_dim >= 0 && d->embed_time_dim <= 16 && d->embed_time_dim % 2 == 0 &&
-                     d->embed_time_dim != 2,
-                 PDEINV_ERR_UNSUPPORTED, "realnvp: embed_time_dim must be 0 or even in [4, 16]");
-  PDEINV_REQUIRE(d->activation >= PDEINV_ACT_CELU && d->activation <= PDEINV_ACT_GELU, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp: unknown activation");
-  PDEINV_REQUIRE(d->masks && d->base_mean && d->base_inv_cov, PDEINV_ERR_INVALID, "realnvp: null host array");
-  PDEINV_REQUIRE(n >= 0 && ld >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID, "realnvp: bad sizes");
-  if (n == 0) return PDEINV_OK;
-  PDEINV_REQUIRE(params && t && x && out, PDEINV_ERR_INVALID, "realnvp: null device pointer");
+// The kernels' view of a checked descriptor
+static NvpArgs nvp_args(const pdeinv_realnvp_desc* d) {
   const int D = d->dim;
   NvpArgs a{};
   a.n_layers = d->n_layers;
@@ -1583,6 +1566,28 @@ extern "C" int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* d, const flo
   for (int k = 0; k < D; ++k) a.mean[k] = d->base_mean[k];
   for (int k = 0; k < D * D; ++k) a.inv_cov[k] = d->base_inv_cov[k];
   for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
+  return a;
+}
+
+}  // namespace pdeinv
+
+using namespace pdeinv;
+
+extern "C" int64_t pdeinv_realnvp_param_count(const pdeinv_realnvp_desc* d) {
+  if (!d || d->dim < 1 || d->dim > 8 || d->n_layers < 1 || d->embed_time_dim < 0) return -1;
+  return nvp_temb_params(d->ignore_time ? 0 : d->embed_time_dim) +
+         (int64_t)d->n_layers * layer_params(d->dim, in_dim_of(d));
+}
+
+extern "C" int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* d, const float* params, const float* t,
+                                         int64_t t_stride, const float* x, int64_t n, int64_t ld, float* out,
+                                         void* stream) {
+  NVP_REQUIRE_DESC(d, "realnvp");
+  PDEINV_REQUIRE(n >= 0 && ld >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID, "realnvp: bad sizes");
+  if (n == 0) return PDEINV_OK;
+  PDEINV_REQUIRE(params && t && x && out, PDEINV_ERR_INVALID, "realnvp: null device pointer");
+  const int D = d->dim;
+  const NvpArgs a = nvp_args(d);
   const int64_t ls = layer_params(D, a.in_dim);
   hipStream_t st = (hipStream_t)stream;
   const dim3 g(grid_for(n));
@@ -1598,13 +1603,12 @@ extern "C" int pdeinv_realnvp_logdensity(const pdeinv_realnvp_desc* d, const flo
 static bool nvp_packed(const pdeinv_realnvp_desc* d) { return d->dim <= 4 && in_dim_of(d) - d->dim <= 12; }
 static NvSlabMap nvp_slab_map(const pdeinv_realnvp_desc* d) {
   NvSlabMap m{};
-  const int E = d->ignore_time ? 0 : d->embed_time_dim;
   m.d = d->dim;
   m.n_t = in_dim_of(d) - d->dim;
   m.pk = nvp_packed(d) ? 1 : 0;
   m.n_layers = d->n_layers;
   m.layer_stride = layer_params(d->dim, in_dim_of(d));
-  m.temb_params = E > 0 ? 2 * ((int64_t)E * E + E) : 0;
+  m.temb_params = nvp_temb_params(d->ignore_time ? 0 : d->embed_time_dim);
   m.n_params = m.temb_params + (int64_t)d->n_layers * m.layer_stride;
   m.cb = m.pk ? NvC<true>::LAYER : NvC<false>::LAYER;
   return m;
@@ -1624,35 +1628,17 @@ extern "C" int64_t pdeinv_realnvp_grad_workspace(const pdeinv_realnvp_desc* d, i
 extern "C" int pdeinv_realnvp_value_and_grad(const pdeinv_realnvp_desc* d, const float* params, const float* t,
                                              int64_t t_stride, const float* x, int64_t n, int64_t ld, float* loss,
                                              float* grad, void* workspace, int64_t workspace_bytes, void* stream) {
-  PDEINV_REQUIRE(d != nullptr, PDEINV_ERR_INVALID, "realnvp: null descriptor");
-  PDEINV_REQUIRE(d->dim >= 1 && d->dim <= 8, PDEINV_ERR_UNSUPPORTED, "realnvp: dim must be in [1, 8]");
-  PDEINV_REQUIRE(d->n_layers >= 1 && d->n_layers <= PDEINV_REALNVP_MAX_LAYERS, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp: 1 <= n_layers <= 64");
-  PDEINV_REQUIRE(d->embed_time_dim >= 0 && d->embed_time_dim <= 16 && d->embed_time_dim % 2 == 0 &&
-                     d->embed_time_dim != 2,
-                 PDEINV_ERR_UNSUPPORTED, "realnvp: embed_time_dim must be 0 or even in [4, 16]");
-  PDEINV_REQUIRE(d->activation >= PDEINV_ACT_CELU && d->activation <= PDEINV_ACT_GELU, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp: unknown activation");
-  PDEINV_REQUIRE(d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp: value_and_grad is built for celu / elu (the flow of log_density_estimation.py:103-114)");
-  PDEINV_REQUIRE(d->masks && d->base_mean && d->base_inv_cov, PDEINV_ERR_INVALID, "realnvp: null host array");
+  NVP_REQUIRE_DESC(
+      d, "realnvp",
+      PDEINV_REQUIRE(d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU, PDEINV_ERR_UNSUPPORTED,
+                     "realnvp: value_and_grad is built for celu / elu (the flow of log_density_estimation.py:103-114)"));
   PDEINV_REQUIRE(n >= 1 && ld >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID,
                  "realnvp: value_and_grad needs n >= 1 rows (the loss is a mean)");
   PDEINV_REQUIRE(params && t && x && loss && grad && workspace, PDEINV_ERR_INVALID, "realnvp: null device pointer");
   PDEINV_REQUIRE(workspace_bytes >= pdeinv_realnvp_grad_workspace(d, n), PDEINV_ERR_INVALID,
                  "realnvp: workspace too small (pdeinv_realnvp_grad_workspace)");
   const int D = d->dim;
-  NvpArgs a{};
-  a.n_layers = d->n_layers;
-  a.ignore_time = d->ignore_time ? 1 : 0;
-  a.E = a.ignore_time ? 0 : d->embed_time_dim;
-  a.in_dim = in_dim_of(d);
-  a.act = d->activation;
-  a.soft_init = d->soft_init;
-  a.log_det = d->base_log_det;
-  for (int k = 0; k < D; ++k) a.mean[k] = d->base_mean[k];
-  for (int k = 0; k < D * D; ++k) a.inv_cov[k] = d->base_inv_cov[k];
-  for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
+  const NvpArgs a = nvp_args(d);
   const int64_t ls = layer_params(D, a.in_dim);
   const int64_t P = pdeinv_realnvp_param_count(d);
   const int64_t rows_max = nvp_grad_rows(n);
@@ -1669,11 +1655,11 @@ extern "C" int pdeinv_realnvp_value_and_grad(const pdeinv_realnvp_desc* d, const
     const int64_t rows = tiles - tile0 < rows_max ? tiles - tile0 : rows_max;
     const dim3 g((unsigned)rows);
     if (packed)
-      hipLaunchKernelGGL((realnvp_grad_kernel<PDEINV_ACT_CELU, true>), g, dim3(kBlock), 0, st, a, D, params, t,
-                         t_stride, x, n, ld, ls, P, tile0, slab, sld);
+      hipLaunchKernelGGL(realnvp_grad_kernel<true>, g, dim3(kBlock), 0, st, a, D, params, t, t_stride, x, n, ld, ls,
+                         P, tile0, slab, sld);
     else
-      hipLaunchKernelGGL((realnvp_grad_kernel<PDEINV_ACT_CELU, false>), g, dim3(kBlock), 0, st, a, D, params, t,
-                         t_stride, x, n, ld, ls, P, tile0, slab, sld);
+      hipLaunchKernelGGL(realnvp_grad_kernel<false>, g, dim3(kBlock), 0, st, a, D, params, t, t_stride, x, n, ld, ls,
+                         P, tile0, slab, sld);
     int rc = check_launch("realnvp_grad_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(nvp_slab_split_kernel, dim3((unsigned)((P + 1 + 63) / 64), kNvSplits), dim3(kBlock), 0, st,
@@ -1692,30 +1678,19 @@ extern "C" int pdeinv_realnvp_value_and_grad(const pdeinv_realnvp_desc* d, const
 // Path selector of the time-derivative entry points (tests and tools/nvp_time_bench.py): 0 = AUTO, 1 = the general
 // per-thread path, 2 = the matrix-core path (UNSUPPORTED outside its envelope). Process-wide.
 static int g_nvp_time_impl = 0;
+// The matrix-core path's envelope. AUTO takes the path wherever it applies, a choice made by measurement: it is
+// faster than the general path on both batches.
 static bool nvp_time_mfma_ok(const pdeinv_realnvp_desc* d) {
   return (d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU) && d->dim <= 4 && !d->ignore_time &&
          d->embed_time_dim >= 4 && d->embed_time_dim <= 12;
 }
-// AUTO takes the matrix-core path only where it measured faster than the general path.
-constexpr bool kNvTimeAutoMfma = true;  // by measurement: faster than the general path on both batches
-static bool nvp_time_auto_mfma(const pdeinv_realnvp_desc* d) { return kNvTimeAutoMfma && nvp_time_mfma_ok(d); }
 
 // Shared by the two time-derivative entry points: n_rows == 0 is the per-sample view (t_stride), n_rows > 0 the
 // sets view (realnvp_time_kernel).
 static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, const float* t, int64_t t_stride,
                            const float* x, int64_t n, int64_t ld, int64_t n_rows, int64_t set_stride, float* logp,
                            float* ds, void* stream) {
-  PDEINV_REQUIRE(d != nullptr, PDEINV_ERR_INVALID, "realnvp_time_derivs: null descriptor");
-  PDEINV_REQUIRE(d->dim >= 1 && d->dim <= 8, PDEINV_ERR_UNSUPPORTED, "realnvp_time_derivs: dim must be in [1, 8]");
-  PDEINV_REQUIRE(d->n_layers >= 1 && d->n_layers <= PDEINV_REALNVP_MAX_LAYERS, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp_time_derivs: 1 <= n_layers <= 64");
-  PDEINV_REQUIRE(d->embed_time_dim >= 0 && d->embed_time_dim <= 16 && d->embed_time_dim % 2 == 0 &&
-                     d->embed_time_dim != 2,
-                 PDEINV_ERR_UNSUPPORTED, "realnvp_time_derivs: embed_time_dim must be 0 or even in [4, 16]");
-  PDEINV_REQUIRE(d->activation >= PDEINV_ACT_CELU && d->activation <= PDEINV_ACT_GELU, PDEINV_ERR_UNSUPPORTED,
-                 "realnvp_time_derivs: unknown activation");
-  PDEINV_REQUIRE(d->masks && d->base_mean && d->base_inv_cov, PDEINV_ERR_INVALID,
-                 "realnvp_time_derivs: null host array");
+  NVP_REQUIRE_DESC(d, "realnvp_time_derivs");
   PDEINV_REQUIRE(n >= 0 && ld >= d->dim && t_stride >= 0 && set_stride >= 0, PDEINV_ERR_INVALID,
                  "realnvp_time_derivs: bad sizes");
   PDEINV_REQUIRE(n <= (int64_t)0x7FFFFFFF * kBlock, PDEINV_ERR_INVALID, "realnvp_time_derivs: too many samples");
@@ -1725,17 +1700,7 @@ static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, co
                      ((uintptr_t)x & 3) == 0 && ((uintptr_t)logp & 3) == 0,
                  PDEINV_ERR_INVALID, "realnvp_time_derivs: misaligned pointer (d_ds needs 8 bytes, the others 4)");
   const int D = d->dim;
-  NvpArgs a{};
-  a.n_layers = d->n_layers;
-  a.ignore_time = d->ignore_time ? 1 : 0;
-  a.E = a.ignore_time ? 0 : d->embed_time_dim;
-  a.in_dim = in_dim_of(d);
-  a.act = d->activation;
-  a.soft_init = d->soft_init;
-  a.log_det = d->base_log_det;
-  for (int k = 0; k < D; ++k) a.mean[k] = d->base_mean[k];
-  for (int k = 0; k < D * D; ++k) a.inv_cov[k] = d->base_inv_cov[k];
-  for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
+  const NvpArgs a = nvp_args(d);
   NvFreq fr{};
   for (int q = 0; q < a.E; ++q)
     fr.w[q] = (float)exp(-(log(10000.0) / (double)(a.E / 2 - 1)) * (double)(q % (a.E / 2)));
@@ -1743,7 +1708,7 @@ static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, co
   hipStream_t st = (hipStream_t)stream;
   PDEINV_REQUIRE(g_nvp_time_impl != 2 || nvp_time_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,
                  "realnvp_time_derivs: the matrix-core path takes celu / elu, dim <= 4, 4 <= E <= 12, no ignore_time");
-  if (g_nvp_time_impl == 2 || (g_nvp_time_impl == 0 && nvp_time_auto_mfma(d))) {
+  if (g_nvp_time_impl != 1 && nvp_time_mfma_ok(d)) {  // forced (checked above), or AUTO inside the envelope
     hipLaunchKernelGGL(realnvp_time_mfma_kernel, dim3(grid_for(n, kNvSPB)), dim3(kBlock), 0, st, a, fr, D, params, t,
                        t_stride, x, n, ld, n_rows, set_stride, ls, logp, ds);
     return check_launch("realnvp_time_mfma_kernel");
@@ -1785,5 +1750,5 @@ extern "C" int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* d, int32_t im
   if (impl >= 0 && impl <= 2) g_nvp_time_impl = impl;
   if (!d) return g_nvp_time_impl;
   if (g_nvp_time_impl == 2) return nvp_time_mfma_ok(d) ? 1 : PDEINV_ERR_UNSUPPORTED;
-  return g_nvp_time_impl == 0 && nvp_time_auto_mfma(d) ? 1 : 0;
+  return g_nvp_time_impl == 0 && nvp_time_mfma_ok(d) ? 1 : 0;
 }

@@ -38,6 +38,7 @@ CASES = [
     (4, "loop", 16, 1.0, False, "silu", 130),
     (3, "random", 6, 1.0, True, "gelu", 64),
     (2, "loop", 10, 1.0, False, "relu", 300),
+    (3, "random", 12, 0.0, False, "elu", 130),
 ]
 
 
@@ -331,12 +332,13 @@ def test_estimate_log_density_takes_a_dataset(native):
     pi.use_learned_log_density(None)
 
 
-PACKED = [c for c in CASES if c[5] == "celu" and c[0] in (2, 4)]
+# the matrix-core envelope, its edges included: d = 1 and 3, E = 4 and 12, soft_init = 0, elu
+PACKED = [c for c in CASES if c[5] in ("celu", "elu") and c[0] <= 4 and 4 <= c[2] <= 12 and c[6] > 1]
 
 
 @pytest.mark.parametrize("case", PACKED, ids=lambda c: f"d{c[0]}-n{c[6]}")
 def test_matrix_core_path_agrees_with_the_general_path(native, case):
-    """The matrix-core path (celu, packed layout d <= 4, E <= 12; n no multiple of its 16-sample tile or 128-sample
+    """The matrix-core path (celu / elu, packed layout d <= 4, 4 <= E <= 12; n no multiple of its 16-sample tile or 128-sample
     block) forced through the selector: against the fp64 restatement at the same tolerance as the general path,
     per-row t and t_stride = 0; against the general path forced on the same inputs; the sets view bit-identical to
     its own per-sample call; two calls of either path bit-identical. Whatever AUTO picks is one of the two."""
