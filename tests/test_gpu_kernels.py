@@ -350,6 +350,20 @@ def test_sde_edge_cases(native):
 LIB, FUSED = 1, 2  # native.MLP_IMPL_LIBRARY / MLP_IMPL_FUSED
 
 
+def _mlp_block_rule(what, dims, flat, zi, zt, z0, true, results, gamma=0.5, total_time=2.0):
+    """The per-block, per-entry and per-slot fp64 rule of tests/mlp_resid_ref.py (|gpu - fp64| <= 16 E, E the fp32
+    restatement's own error) on the (acc, grad) pairs `results` of one residual call per implementation. The reference
+    takes the parameters and the true potential as the kernels are given them: rounded to fp32. Nets 1000 wide and
+    wider take two orders of the restatement instead of four (the cost of the CPU reference)."""
+    import mlp_resid_ref as RR
+    f = lambda a: np.asarray(a).astype(np.float32).astype(np.float64)  # noqa: E731
+    case = RR.Case(dims, nr.mlp_unflat(f(flat), dims), [z0, zi, zt],
+                   RR.coefficients(len(z0), len(zi), len(zt), gamma, total_time), (true[0], f(true[1])),
+                   n_orders=2 if dims[1] >= 1000 else RR.N_ORDERS)
+    for name, (acc, grad) in results.items():
+        case.check(f"{what} {dims} {name}", grad.cpu().numpy(), acc.cpu().numpy())
+
+
 @pytest.mark.parametrize("dims,true_kind,chunk,impl", [
     ([2, 16, 16, 5], "gmm", 1000, LIB), ([4, 32, 32, 40], "quad", 1 << 18, LIB),
     ([8, 64, 64, 64, 40], "gmm", 777, LIB), ([8, 256, 256, 40], "gmm", 1 << 18, LIB),
@@ -375,7 +389,9 @@ def test_residual_mlp_vs_restatement(native, dims, true_kind, chunk, impl):
     FD-checked in tests/test_oracle.py, on both implementations (rocBLAS library path and the
     fused MFMA path). Multi-chunk paths exercised (chunk < rows); L = 3 covers the middle layers.
     impl = 0 (AUTO) on out-of-envelope shapes must take the hand-written path: its result equals
-    impl = FUSED bit for bit (the fused path is deterministic), no rocBLAS."""
+    impl = FUSED bit for bit (the fused path is deterministic), no rocBLAS.
+    Beside the whole-vector bounds the gradient is held per parameter block and entry, and the accumulator per slot,
+    to 16 x the fp32 restatement's own error against fp64 (_mlp_block_rule, tests/mlp_resid_ref.py)."""
     rng = np.random.default_rng(len(dims) + dims[1])
     d = dims[0]
     flat = np.concatenate([np.concatenate([rng.standard_normal((dims[i], dims[i + 1])).ravel() * np.sqrt(1.0 / dims[i]),
@@ -405,6 +421,8 @@ def test_residual_mlp_vs_restatement(native, dims, true_kind, chunk, impl):
     g = grad.cpu().numpy()
     assert np.max(np.abs(g - g_ref)) < 2e-3 * (1 + np.abs(g_ref).max()), np.max(np.abs(g - g_ref))
     assert abs(out[2] - np.linalg.norm(g_ref)) < 2e-3 * (1 + np.linalg.norm(g_ref))
+    _mlp_block_rule("restatement", dims, flat, zi, zt, z0, (true_kind, mus if true_kind == "gmm" else F),
+                    {{LIB: "LIBRARY", FUSED: "FUSED", 0: "AUTO"}[impl]: (acc, grad)})
 
 
 def test_auto_never_reaches_rocblas(native):
@@ -489,6 +507,8 @@ def test_residual_mlp_boundary_sets_span_chunks(native, dims):
     a, al = acc.cpu().numpy(), acc_l.cpu().numpy()
     assert np.allclose(a, al, rtol=2e-4, atol=1e-5 * np.abs(al).max())
     assert np.max(np.abs(g - grad_l.cpu().numpy())) < 2e-4 * (1 + np.abs(g_ref).max())
+    _mlp_block_rule("boundary sets", dims, flat, zi, zt, z0, ("quad", F),
+                    {"FUSED": (acc, grad), "LIBRARY": (acc_l, grad_l)})
 
 
 def test_residual_mlp_fused_matches_library(native):
