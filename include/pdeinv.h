@@ -51,7 +51,7 @@ extern "C" {
  * PDEINV_POT_MLP, pdeinv_mlp_shape, pdeinv_mlp_potential(_path, _workspace_bytes),
  * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes); PDEINV_POT_MEANFIELD_MLP,
  * pdeinv_mf_mlp_supported, pdeinv_mf_mlp_workspace_bytes, pdeinv_mf_mlp_prepare, pdeinv_mf_mlp_force,
- * pdeinv_mf_mlp_step. */
+ * pdeinv_mf_mlp_step; pdeinv_realnvp_map, pdeinv_realnvp_map_path (additive as well: the version stays 10). */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -719,6 +719,26 @@ int pdeinv_realnvp_time_derivs_sets(const pdeinv_realnvp_desc* desc, const float
 #define PDEINV_NVP_TIME_GENERAL 1
 #define PDEINV_NVP_TIME_MATRIX 2
 int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* desc, int32_t impl);
+
+/* The flow as a map, in either direction (MNF.__call__(t, x0, reverse), normalizing_flow.py:209-221), per sample i:
+ *   reverse = 1: layers L-1 .. 0, x <- (x + tr) e^s,  ldj += sum s  (the likelihood direction: data -> latent)
+ *   reverse = 0: layers 0 .. L-1, x <- x e^{-s} - tr, ldj -= sum s  (generation: latent x0 -> a point at time t_i)
+ * d_y[i * ld_y + k] = the image (k < dim; floats of a row beyond dim are not written; ld_y == 0: dim), d_ldj[i] =
+ * the log-determinant sum, d_logp[i] = the log-density, under the flow, of the point that lies in data space:
+ *   reverse = 1: log p0(y_i) + ldj_i (= pdeinv_realnvp_logdensity of x_i);  reverse = 0: log p0(x_i) - ldj_i.
+ * d_y, d_ldj, d_logp are each nullable (at least one must be given). d_y == d_x with ld_y == ld_x is allowed (in
+ * place); any other overlap is the caller's error. t_stride 0 broadcasts d_t[0]. n == 0 is a no-op. Plain stores,
+ * no atomics: a sample's outputs depend on its row, its t and the parameters only (not on n or its position).
+ * impl: PDEINV_NVP_TIME_AUTO / _GENERAL / _MATRIX, per call (stateless: no process-wide selector). The general
+ * path (one thread per sample) takes the whole envelope of pdeinv_realnvp_logdensity, and its d_logp for reverse =
+ * 1 is that entry point's, bit for bit; the matrix-core path takes celu / elu flows (any dim <= 8, any E,
+ * ignore_time), else UNSUPPORTED. AUTO takes the matrix-core path only where it measured faster. All argument
+ * checks run before any device call. pdeinv_realnvp_map_path: the path `desc` takes under `impl`: 0 general, 1
+ * matrix-core, or a negative status; no device call. */
+int pdeinv_realnvp_map_path(const pdeinv_realnvp_desc* desc, int32_t impl);
+int pdeinv_realnvp_map(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_t, int64_t t_stride,
+                       const float* d_x, int64_t n, int64_t ld_x, int32_t reverse, int32_t impl, float* d_y,
+                       int64_t ld_y, float* d_ldj, float* d_logp, void* stream);
 
 /* Maximum-likelihood value_and_grad of the flow (replaces jax.value_and_grad(loss_fn) in
  * core/log_density_estimation.py:47-58): *d_loss = -mean_i log p_{t_i}(x_i), d_grad[param_count]

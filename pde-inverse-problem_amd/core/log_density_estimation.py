@@ -10,7 +10,8 @@ parameter gradient on the HIP kernel `pdeinv_realnvp_value_and_grad` (replacing
 jax.value_and_grad) and takes an Adam step (b1 = 0.9, eps = 1e-4) on the fused native update,
 with the reference's constant / cosine / constant learning-rate schedule (:116-145). Epoch losses
 stay on the device and are fetched once per print interval. The closing density plot
-(plot_trajectory_of_distributions, matplotlib + wandb) is out of scope.
+(plot_trajectory_of_distributions, matplotlib + wandb) is out of scope; `flow_moment_error` is its numeric
+stand-in (moments of flow samples against the data's, per time stamp).
 """
 from __future__ import annotations
 
@@ -52,7 +53,8 @@ def create_custom_schedule(lr, T0, T1):
 
 def make_log_density_fn(model: RealNVP, params):
     """log_density_fn(t, x) of a flow and its parameters, as estimate_log_density returns it: .model, .params and
-    .partial_s(t, x) -> (ds log p, ds2 log p) (pdeinv_realnvp_time_derivs)."""
+    .partial_s(t, x) -> (ds log p, ds2 log p) (pdeinv_realnvp_time_derivs), .sample(key, t, n) -> (x, log p) and
+    .inverse(t, x) -> (x0, ldj) (pdeinv_realnvp_map)."""
     def log_density_fn(t, x):
         return model.apply(params, t, x)
 
@@ -63,7 +65,55 @@ def make_log_density_fn(model: RealNVP, params):
     log_density_fn.params = params
     log_density_fn.model = model
     log_density_fn.partial_s = partial_s
+    log_density_fn.sample = lambda key, t, n, **kw: model.sample(params, key, t, n, **kw)
+    log_density_fn.inverse = lambda t, x: model.inverse(params, t, x)
     return log_density_fn
+
+
+def _moments_of_sets(rows, n_sets, n_rows, d):
+    """(mean [n_sets, d], cov [n_sets, d, d]) fp64 of the row sets of a contiguous [n_sets * n_rows, >= d] tensor,
+    from one native.moments_batched call ([count, sum x, sum x_i x_j (i <= j)] per set)."""
+    ld = rows.stride(0)
+    mom = native.moments_batched(rows, n_sets, n_rows, d, n_rows * ld, ld)
+    cnt = mom[:, :1]
+    mean = mom[:, 1:1 + d] / cnt
+    iu = torch.triu_indices(d, d, device=mom.device)
+    second = torch.zeros((n_sets, d, d), device=mom.device, dtype=mom.dtype)
+    second[:, iu[0], iu[1]] = mom[:, 1 + d:]
+    second[:, iu[1], iu[0]] = mom[:, 1 + d:]
+    cov = second / cnt[:, :, None] - mean[:, :, None] * mean[:, None, :]
+    return mean, cov
+
+
+def flow_sample_moments(log_density_fn, key, taus, n_per_time):
+    """(mean [n_t, d], cov [n_t, d, d]) (fp64, population covariance) of n_per_time flow samples per time stamp in
+    `taus`: one `sample` call over all stamps with t repeated, one native.moments_batched call."""
+    model = log_density_fn.model
+    d = model.mnf.dim
+    dev = log_density_fn.params["params"].device
+    taus = torch.as_tensor(taus, dtype=torch.float32, device=dev).reshape(-1)
+    n_t, n = taus.numel(), int(n_per_time)
+    x, _ = log_density_fn.sample(key, taus.repeat_interleave(n), n_t * n)
+    return _moments_of_sets(x, n_t, n, d)
+
+
+def flow_moment_error(log_density_fn, key, dataset, time_index, n_per_time):
+    """The numeric stand-in for the reference's closing density plot: per time stamp in `time_index` of
+    dataset {"0T_tm": [n_time, n_traj, >= d] time-major, "tau_0T": [n_traj, n_time]}, the relative errors (Frobenius
+    norm) of the mean and covariance of n_per_time flow samples against those of the dataset's x-rows at that stamp
+    (the stamp's time: the mean of its tau column). Returns (err_mean [n_t], err_cov [n_t]) fp64."""
+    model = log_density_fn.model
+    d = model.mnf.dim
+    traj = dataset["0T_tm"]
+    ti = torch.as_tensor(np.asarray(time_index), device=traj.device, dtype=torch.long).reshape(-1)
+    rows = traj[ti].contiguous()                                  # [n_t, n_traj, w]
+    n_t, n_traj, w = rows.shape
+    taus = dataset["tau_0T"].to(traj.device)[:, ti].double().mean(0)
+    m_d, c_d = _moments_of_sets(rows.reshape(n_t * n_traj, w), n_t, n_traj, d)
+    m_f, c_f = flow_sample_moments(log_density_fn, key, taus, n_per_time)
+    err_mean = torch.linalg.vector_norm(m_f - m_d, dim=-1) / torch.linalg.vector_norm(m_d, dim=-1)
+    err_cov = torch.linalg.matrix_norm(c_f - c_d) / torch.linalg.matrix_norm(c_d)
+    return err_mean, err_cov
 
 
 def estimate_log_density(cfg, pde_instance, rng, num_epochs: int = 20000, frequency: int = 100, verbose=True,

@@ -4,7 +4,8 @@ Same constructor arguments and call convention as the reference's flax modules:
 `MNF(dim, couple_mul, mask_type, soft_init, ignore_time, activation_layer, embed_time_dim)` and
 `RealNVP(mnf, log_prob_0)`; `init(key, t, x) -> params`, `apply(params, t, x) -> log p_t(x)` for a
 single (t, x) or batched rows (the reference vmaps the same call). The evaluation is the HIP
-kernel `pdeinv_realnvp_logdensity` (one thread per sample, VALU); params are a flat fp32 device
+kernel `pdeinv_realnvp_logdensity` (one thread per sample, VALU); `MNF.apply(params, t, x, reverse)` is the flow
+as a two-way map (`pdeinv_realnvp_map`), with `RealNVP.inverse / forward / sample` on it; params are a flat fp32 device
 vector in the layout documented in include/pdeinv.h. `log_prob_0` must be a `core.distribution.Gaussian`
 (the reference passes `distribution_initial_x.logdensity`, log_density_estimation.py:22).
 """
@@ -95,6 +96,32 @@ class MNF:
         assert flat.size == self.param_count()
         return {"params": torch.as_tensor(flat, dtype=torch.float32, device=device)}
 
+    def _map_desc(self):
+        """Descriptor of the flow alone: a standard-normal base that `apply` never reads (it asks for no logp)."""
+        if getattr(self, "_desc", None) is None:
+            self._desc, self._keep = native.realnvp_desc(
+                self.dim, self.masks, self.embed_time_dim, self.ignore_time, self.soft_init, self.activation_layer,
+                np.zeros(self.dim), np.eye(self.dim), float(self.dim * np.log(2 * np.pi)))
+        return self._desc
+
+    def apply(self, params, t, x, reverse=False):
+        """The reference's MNF.__call__(t, x0, reverse) (:205-221) -> (x_out, ldj_sum): reverse=False generates the
+        point at time t with X(0) = x, reverse=True is the likelihood direction. The HIP kernel
+        `pdeinv_realnvp_map`; a single (t, x) or batched rows like `RealNVP.apply`."""
+        return _flow_map(self._map_desc(), params, t, x, reverse, ("y", "ldj"))
+
+    __call__ = apply
+
+
+def _flow_map(desc, params, t, x, reverse, want):
+    flat = params["params"] if isinstance(params, dict) else params
+    x = torch.as_tensor(x, dtype=torch.float32, device=flat.device)
+    single = x.dim() == 1
+    rows = x.reshape(1, -1) if single else x
+    tt = torch.as_tensor(t, dtype=torch.float32, device=flat.device).reshape(-1)
+    res = native.realnvp_map(desc, flat, tt, rows, reverse, want=want)
+    return tuple(res[k][0] if single else res[k] for k in want)
+
 
 class RealNVP:
     """log p_t(x) = log p0(T_t^{-1}(x)) + sum ldj (:223-229)."""
@@ -122,6 +149,26 @@ class RealNVP:
         tt = torch.as_tensor(t, dtype=torch.float32, device=flat.device).reshape(-1)
         out = native.realnvp_logdensity(self._desc, flat, tt, rows)
         return out[0] if single else out
+
+    def inverse(self, params, t, x):
+        """(x0, ldj): the latent point of x at time t and the log-determinant sum (the likelihood direction of
+        `pdeinv_realnvp_map`); log p_t(x) = log p0(x0) + ldj."""
+        return _flow_map(self._desc, params, t, x, True, ("y", "ldj"))
+
+    def forward(self, params, t, x0):
+        """(x, log p_t(x)): the point at time t with X(0) = x0 and its log-density under the flow (generation)."""
+        return _flow_map(self._desc, params, t, x0, False, ("y", "logp"))
+
+    def sample(self, params, key: prng.Key, t, n: int, row_offset: int = 0, counter_offset: int = 0):
+        """n draws from the learned density at time t (a scalar or an [n] tensor) and their log-density: the base
+        draw x0 = Gaussian.sample(n, key, row_offset, counter_offset) (the `pdeinv_gaussian_sample` stream, so ranks
+        shard by row_offset) pushed through `pdeinv_realnvp_map(reverse=0)`. Returns (x [n, dim], logp [n])."""
+        g = self.log_prob_0.__self__ if hasattr(self.log_prob_0, "__self__") else self.log_prob_0
+        x0 = g.sample(int(n), key, row_offset=row_offset, counter_offset=counter_offset)
+        flat = params["params"] if isinstance(params, dict) else params
+        tt = torch.as_tensor(t, dtype=torch.float32, device=flat.device).reshape(-1)
+        res = native.realnvp_map(self._desc, flat, tt, x0, False, out=x0, want=("y", "logp"))
+        return res["y"], res["logp"]
 
     def time_derivatives(self, params, t, x):
         """(log p_t(x), d/dt log p_t(x), d2/dt2 log p_t(x)) — what jax.grad(log_density_fn, 0) taken twice gives in

@@ -1,4 +1,4 @@
-// realnvp.hip — the time-conditioned RealNVP flow (core/normalizing_flow.py:8-229) in three parts:
+// realnvp.hip — the time-conditioned RealNVP flow (core/normalizing_flow.py:8-229) in four parts:
 //  1. realnvp_logdensity_kernel: log p_t(x), one thread per (t, x) sample, the tiny MLPs (widths 8 / 16 / 16,
 //     SURVEY.md §8(a) a12) in VGPRs on the VALU, weights at wave-uniform addresses (scalar loads). Helpers:
 //     nvp_act, dense, basic_mlp.
@@ -8,10 +8,13 @@
 //  3. The time derivatives (log p, d/dt, d2/dt2): realnvp_time_kernel (general, one thread per sample; helpers
 //     nvp_act_d2, nvp_act3, dense3_*, basic_mlp3) and realnvp_time_mfma_kernel (matrix cores; nv_fwdT3, nv_bias3,
 //     nv_celu3, nv_mlp_fwd3 on part 2's tile machinery).
+//  4. The flow as a map in either direction (y, ldj, log p; pdeinv_realnvp_map): realnvp_map_kernel (general, one
+//     thread per sample, part 1's arithmetic over a compile-time direction) and realnvp_map_mfma_kernel (matrix
+//     cores: part 2's likelihood pass on its tile machinery, run forwards or backwards through the layers).
 // Shared: NvpArgs (masks and the base Gaussian travel in the kernel arguments) and nvp_temb_params by all;
-// the block-level staging nv_lane / nv_stage_* by the two tile kernels; the three-stream arithmetic nvp_act3,
+// the block-level staging nv_lane / nv_stage_* by the three tile kernels; the three-stream arithmetic nvp_act3,
 // NVP_COUPLE3 and NVP_BASE_STORE3 (macros: see there) by the two time kernels; one descriptor
-// check (NVP_REQUIRE_DESC) and one NvpArgs fill (nvp_args) by the three host entry points.
+// check (NVP_REQUIRE_DESC) and one NvpArgs fill (nvp_args) by the host entry points.
 // Still written twice, on purpose: the time embedding's forward (sinusoid, bias, nv_fwdT, celu) in
 // realnvp_grad_kernel, once for the likelihood pass and once for the backward (see the comment at the second), and
 // the three lines of sample addressing (per-sample / sets view) in the two time kernels.
@@ -150,6 +153,117 @@ __global__ __launch_bounds__(kBlock) void realnvp_logdensity_kernel(NvpArgs a, c
     quad = fmaf(x[r] - a.mean[r], acc, quad);
   }
   out[i] = -0.5f * (a.log_det + quad) + ldj;
+}
+
+// (x - mean)^T inv_cov (x - mean) of the base Gaussian
+template <int D>
+__device__ __forceinline__ float nvp_base_quad(const NvpArgs& a, const float (&x)[D]) {
+  float quad = 0.f;
+#pragma unroll
+  for (int r = 0; r < D; ++r) {
+    float acc = 0.f;
+#pragma unroll
+    for (int c = 0; c < D; ++c) acc = fmaf(a.inv_cov[r * D + c], x[c] - a.mean[c], acc);
+    quad = fmaf(x[r] - a.mean[r], acc, quad);
+  }
+  return quad;
+}
+
+// The flow as a map, one kernel body over the direction (pdeinv_realnvp_map's general path), with the arithmetic
+// of realnvp_logdensity_kernel statement for statement: <D, 1>'s out is that kernel's, bit for bit. (That kernel is
+// not this body's (REV = 1, no y) case: compiled from this body it moves a 16-float array into LDS, 16 KB per block.)
+//   REV = 1: layers L-1 .. 0, x <- (x + tr) e^s,  ldj += sum s, out = log p0(y) + ldj    (likelihood direction)
+//   REV = 0: layers 0 .. L-1, x <- x e^{-s} - tr, ldj -= sum s, out = log p0(x_in) - ldj (generation)
+// y (row stride ld_y), ldj_out and out are each nullable. y may be xv itself (in place: a thread has read its row
+// before it writes it), so neither pointer is restrict.
+template <int D, int REV>
+__global__ __launch_bounds__(kBlock) void realnvp_map_kernel(NvpArgs a, const float* __restrict__ params,
+                                                                    const float* __restrict__ tv, int64_t t_stride,
+                                                                    const float* xv, int64_t n, int64_t ld,
+                                                                    int64_t layer_stride, float* y, int64_t ld_y,
+                                                                    float* __restrict__ ldj_out,
+                                                                    float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float t = tv[i * t_stride];
+  float x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = xv[i * ld + k];
+  float quad = 0.f;  // the base quadratic form of the point in latent space: the input (REV = 0) or the output
+  if (!REV && out) quad = nvp_base_quad<D>(a, x);
+  // time embedding (shared by every coupling layer)
+  float temb[16];
+  const float* p = params;
+  if (!a.ignore_time) {
+    if (a.E > 0) {
+      const int half = a.E / 2;
+      const float step = logf(10000.f) / (float)(half - 1);
+      float se[16], h[16];
+      for (int k = 0; k < half; ++k) {
+        const float e = t * expf(-step * (float)k);
+        se[k] = sinf(e);
+        se[half + k] = cosf(e);
+      }
+      // two E x E dense layers (runtime E <= 16)
+      for (int o = 0; o < a.E; ++o) h[o] = p[a.E * a.E + o];
+      for (int q = 0; q < a.E; ++q)
+        for (int o = 0; o < a.E; ++o) h[o] = fmaf(se[q], p[q * a.E + o], h[o]);
+      for (int o = 0; o < a.E; ++o) h[o] = nvp_act(a.act, h[o]);
+      p += a.E * a.E + a.E;
+      for (int o = 0; o < a.E; ++o) temb[o] = p[a.E * a.E + o];
+      for (int q = 0; q < a.E; ++q)
+        for (int o = 0; o < a.E; ++o) temb[o] = fmaf(h[q], p[q * a.E + o], temb[o]);
+      p += a.E * a.E + a.E;
+    } else {
+      temb[0] = t;
+    }
+  }
+  const float* layers = p;
+  float ldj = 0.f;
+  for (int j = 0; j < a.n_layers; ++j) {
+    const int l = REV ? a.n_layers - 1 - j : j;  // likelihood direction: reversed layers
+    const float* lp = layers + (int64_t)l * layer_stride;
+    const float* m = a.masks + l * D;
+    float in[D + 16];
+#pragma unroll
+    for (int k = 0; k < D; ++k) in[k] = x[k] * m[k];
+    const int n_t = a.in_dim - D;
+    for (int q = 0; q < n_t; ++q) in[D + q] = temb[q];
+    float s[D], tr[D];
+    const float* sfp = lp;
+    const float* q = basic_mlp<D>(lp + D, in, a.in_dim, a.act, s);
+    basic_mlp<D>(q, in, a.in_dim, a.act, tr);
+    const bool hard = !a.ignore_time && a.soft_init == 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      float sk = hard ? t * s[k] : s[k];
+      float tk = hard ? t * tr[k] : tr[k];
+      const float sf = expf(sfp[k]);
+      sk = tanhf(sk / sf) * sf;
+      sk *= 1.f - m[k];
+      tk *= 1.f - m[k];
+      if (REV) {
+        x[k] = (x[k] + tk) * expf(sk);
+        ldj += sk;
+      } else {
+        x[k] = x[k] * expf(-sk) - tk;
+        ldj -= sk;
+      }
+    }
+  }
+  if (y) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) y[i * ld_y + k] = x[k];
+  }
+  if (ldj_out) ldj_out[i] = ldj;
+  if (REV) {
+    if (out) {
+      quad = nvp_base_quad<D>(a, x);
+      out[i] = -0.5f * (a.log_det + quad) + ldj;
+    }
+  } else if (out) {
+    out[i] = -0.5f * (a.log_det + quad) - ldj;
+  }
 }
 
 
@@ -1525,6 +1639,215 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The flow as a map on the matrix cores (pdeinv_realnvp_map's matrix-core path; celu / elu, either layout): the
+// likelihood pass of realnvp_grad_kernel run in either direction, and nothing else of that kernel. 16-sample tiles
+// in the v_mfma_f32_16x16x4_f32 accumulator layout, the layer image NvM<PK> staged through the nv_layer_dst table
+// (the next layer's parameters in registers under this layer's math; no transposed copies), both nets through
+// nv_mlp_fwd<PK>, the coupling update on the lanes that own coordinates, on the hardware exp2 / rcp as in the
+// gradient kernel. A wave carries G groups of kNvT tiles through each staged layer (16 kNvT G samples per wave).
+//   REV = 1: staging order L-1 .. 0, x <- (x + tr) e^s,  ldj += sum s, logp = log p0(y) + ldj
+//   REV = 0: staging order 0 .. L-1, x <- x e^{-s} - tr, ldj -= sum s, logp = log p0(x_in) - ldj
+// Base form: every lane gathers its sample's coordinates from the owning lanes (__shfl), as the time kernel does.
+// Stores: the owning lanes write y (packed: lane group c coordinate c; identity: lane group q coordinates
+// 4q .. 4q + 3, one float4 where y_vec says that rows and pointer are 16-byte aligned), lane group 0 ldj and logp.
+// Plain stores, no atomics; a sample's outputs depend on its own column of the tiles only. y may be xv (in place).
+// ---------------------------------------------------------------------------------------------
+#ifndef PDEINV_NVP_MAP_GROUPS
+#define PDEINV_NVP_MAP_GROUPS 1
+#endif
+constexpr int kNvMapG = PDEINV_NVP_MAP_GROUPS;  // groups of kNvT tiles per wave and staged layer
+constexpr int kNvMapSPB = kNvSPB * kNvMapG;     // samples per block
+constexpr int kNvWavesMapPk = 4;                // waves per SIMD, packed layout
+constexpr int kNvWavesMap = 3;                  // waves per SIMD, identity layout (at 4 it spills)
+
+template <bool PK, int REV>
+__global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void realnvp_map_mfma_kernel(
+    NvpArgs a, int d, const float* __restrict__ params, const float* __restrict__ tv, int64_t t_stride,
+    const float* xv, int64_t n, int64_t ld, int64_t layer_stride, float* y, int64_t ld_y, int y_vec,
+    float* __restrict__ ldj_out, float* __restrict__ logp_out) {
+  using M = NvM<PK>;
+  constexpr int G = kNvMapG;
+  constexpr int NC = PK ? 1 : 4;    // registers that hold coordinates
+  constexpr int DMAX = PK ? 4 : 8;  // coordinates a layout can hold
+  __shared__ float sW[M::LAYER];    // current coupling layer (padded); the time embedding before the first
+  __shared__ float sF[48];          // sinusoid table: frequency, sin weight, cos weight
+  __shared__ uint32_t sDst[kNvRaw];
+  const int E = a.E, n_t = a.in_dim - d, L = a.n_layers;
+  const float* layers = params + nvp_temb_params(E);
+  const bool hard = !a.ignore_time && a.soft_init == 0.f;
+  const int tid = threadIdx.x, wave = tid >> 6;
+  const NvLane ln = nv_lane(tid, false);
+  nv_stage_sinusoid(sF, E, [E](int q) {  // fp32 on the device, as the gradient kernel
+    const int half = E / 2;
+    const float step = logf(10000.f) / (float)(half - 1);
+    return expf(-step * (float)(q < half ? q : q - half));
+  });
+  nv_stage_init<PK>(sDst, sW, layer_stride, d, n_t);
+  float pre[kNvPre];
+  auto prefetch = [&](int l) {
+    const float* lp = layers + (int64_t)l * layer_stride;
+#pragma unroll
+    for (int k = 0; k < kNvPre; ++k) {
+      const int q = tid + k * kBlock;
+      pre[k] = q < layer_stride ? lp[q] : 0.f;
+    }
+  };
+  prefetch(REV ? L - 1 : 0);
+  __syncthreads();  // sW zeroed
+  if (E > 0) nv_stage_temb<PK>(sW, params, E, false);
+  __syncthreads();
+  // base quadratic form of the sample in lane column s: (x - mean)^T inv_cov (x - mean), in every lane
+  auto base_quad = [&](const f32x4& xu) {
+    float xc[DMAX];
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+      const float v = __shfl(PK ? xu[0] : xu[k & 3], 16 * (PK ? k : k >> 2) + ln.s, 64);
+      xc[k] = k < d ? v - a.mean[k] : 0.f;
+    }
+    float quad = 0.f;
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+      if (r < d) {
+        float acc = 0.f;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+          if (c < d) acc = fmaf(a.inv_cov[r * d + c], xc[c], acc);
+        quad = fmaf(xc[r], acc, quad);
+      }
+    }
+    return quad;
+  };
+  // ---- the wave's tiles ----
+  NvV x[G], temb[G];
+  float tt[G][kNvT], ldj[G][kNvT], quad[G][kNvT];
+  const int64_t base = (int64_t)blockIdx.x * kNvMapSPB + wave * 16 * kNvT * G;
+#pragma unroll
+  for (int gi = 0; gi < G; ++gi)
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+      const int64_t i = base + 16 * (gi * kNvT + u) + ln.s;
+      const bool active = i < n;
+      tt[gi][u] = active ? tv[i * t_stride] : 0.f;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int k = nv_xinv<PK>(4 * ln.g + c, d);
+        x[gi][u][c] = (active && k >= 0 && (!PK || c == 0)) ? xv[i * ld + k] : 0.f;  // packed: registers 1..3 are 0
+      }
+      ldj[gi][u] = 0.f;
+      quad[gi][u] = (!REV && logp_out) ? base_quad(x[gi][u]) : 0.f;
+    }
+  if (E > 0) {  // TimeEmbedding (:8-22)
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+      NvV se, he;
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int q = 4 * ln.g + c;
+          const float e = tt[gi][u] * sF[q];
+          se[u][c] = sF[16 + q] * sinf(e) + sF[32 + q] * cosf(e);
+        }
+      nv_bcast(he, nv_vec(sW + M::E_B1, ln));
+      nv_fwdT(sW + M::E_W1, ln, se, he);
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
+      nv_bcast(temb[gi], nv_vec(sW + M::E_B2, ln));
+      nv_fwdT(sW + M::E_W2, ln, he, temb[gi]);
+    }
+    __syncthreads();  // every wave has read the time embedding: back to the zero-padded layer image
+    for (int q = tid; q < M::TEMB; q += kBlock) sW[q] = 0.f;
+  } else {
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi)
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          temb[gi][u][c] = (!a.ignore_time && 4 * ln.g + c == nv_tpos<PK>(0)) ? tt[gi][u] : 0.f;
+  }
+  for (int j = 0; j < L; ++j) {
+    const int l = REV ? L - 1 - j : j;
+    __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
+    nv_stage_mask<PK>(sW, a, l, d);
+#pragma unroll
+    for (int k = 0; k < kNvPre; ++k) {
+      const int q = tid + k * kBlock;
+      if (q < layer_stride) sW[sDst[q] & 0xFFFFu] = pre[k];
+    }
+    if (j + 1 < L) prefetch(REV ? l - 1 : l + 1);
+    __syncthreads();
+    const f32x4 m = nv_vec(sW + M::MASK, ln);
+    const f32x4 sfw = nv_vec(sW + M::SF, ln);
+    f32x4 sf, isf;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      sf[c] = nv_exp(sfw[c]);
+      isf[c] = __builtin_amdgcn_rcpf(sf[c]);
+    }
+#pragma unroll
+    for (int gi = 0; gi < G; ++gi) {
+      NvV xm, so, to;
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[gi][u][0] * m[0], 0.f, 0.f, 0.f} : x[gi][u] * m;
+      {
+        NvAct h;
+        nv_mlp_fwd<PK>(sW + M::SNET, ln, temb[gi], xm, h, so);
+        nv_mlp_fwd<PK>(sW + M::TNET, ln, temb[gi], xm, h, to);
+      }
+#pragma unroll
+      for (int u = 0; u < kNvT; ++u) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {  // padded / masked coordinates: keep = 0, x unchanged
+          const float keep = 1.f - m[c];
+          const float th = hard ? tt[gi][u] : 1.f;
+          const float sk = nv_tanh(th * so[u][c] * isf[c]) * sf[c] * keep;
+          const float tr = th * to[u][c] * keep;
+          if (REV) {
+            x[gi][u][c] = (x[gi][u][c] + tr) * nv_exp(sk);
+            ldj[gi][u] += sk;
+          } else {
+            x[gi][u][c] = x[gi][u][c] * nv_exp(-sk) - tr;
+            ldj[gi][u] -= sk;
+          }
+        }
+      }
+    }
+  }
+  // ---- outputs ----
+#pragma unroll
+  for (int gi = 0; gi < G; ++gi)
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+      const int64_t i = base + 16 * (gi * kNvT + u) + ln.s;
+      const bool active = i < n;
+      float lj = ldj[gi][u];  // the four lane groups' parts
+      lj += __shfl_xor(lj, 16, 64);
+      lj += __shfl_xor(lj, 32, 64);
+      float lp = 0.f;
+      if (logp_out) lp = REV ? -0.5f * (a.log_det + base_quad(x[gi][u])) + lj : -0.5f * (a.log_det + quad[gi][u]) - lj;
+      if (active && ln.g == 0) {
+        if (ldj_out) ldj_out[i] = lj;
+        if (logp_out) logp_out[i] = lp;
+      }
+      if (active && y) {
+        float* yr = y + i * ld_y;
+        if constexpr (PK) {
+          if (ln.g < d) yr[ln.g] = x[gi][u][0];
+        } else {
+          if (y_vec && 4 * ln.g + 3 < d) {
+            *reinterpret_cast<f32x4*>(yr + 4 * ln.g) = x[gi][u];
+          } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+              if (4 * ln.g + c < d) yr[4 * ln.g + c] = x[gi][u][c];
+          }
+        }
+      }
+    }
+}
+
 static int64_t layer_params(int D, int in_dim) {
   const int64_t mlp = (int64_t)in_dim * 8 + 8 + 8 * 16 + 16 + 16 * 16 + 16 + 16 * D + D;
   return D + 2 * mlp;
@@ -1751,4 +2074,68 @@ extern "C" int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* d, int32_t im
   if (!d) return g_nvp_time_impl;
   if (g_nvp_time_impl == 2) return nvp_time_mfma_ok(d) ? 1 : PDEINV_ERR_UNSUPPORTED;
   return g_nvp_time_impl == 0 && nvp_time_mfma_ok(d) ? 1 : 0;
+}
+
+// ---- the flow as a map (pdeinv_realnvp_map) ----
+// The matrix-core path's envelope: that of pdeinv_realnvp_value_and_grad (celu / elu; any dim <= 8, any E,
+// ignore_time; packed layout where nvp_packed holds, identity layout otherwise).
+static bool nvp_map_mfma_ok(const pdeinv_realnvp_desc* d) {
+  return d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU;
+}
+// AUTO's rule, a choice made by measurement: the matrix-core path where it measured faster than
+// the general path on every batch of the descriptor class.
+static bool nvp_map_auto_mfma(const pdeinv_realnvp_desc* d) { return nvp_map_mfma_ok(d); }
+
+// 0 general, 1 matrix-core, or a negative status (who: the entry point's message prefix)
+#define NVP_MAP_PATH(d, impl, who, path)                                                                     \
+  NVP_REQUIRE_DESC(d, who);                                                                                  \
+  PDEINV_REQUIRE((impl) == PDEINV_NVP_TIME_AUTO || (impl) == PDEINV_NVP_TIME_GENERAL ||                      \
+                     (impl) == PDEINV_NVP_TIME_MATRIX,                                                       \
+                 PDEINV_ERR_INVALID, who ": impl must be PDEINV_NVP_TIME_AUTO, _GENERAL or _MATRIX");        \
+  PDEINV_REQUIRE((impl) != PDEINV_NVP_TIME_MATRIX || nvp_map_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,             \
+                 who ": the matrix-core path takes celu / elu flows");                                       \
+  const int path = (impl) == PDEINV_NVP_TIME_MATRIX || ((impl) == PDEINV_NVP_TIME_AUTO && nvp_map_auto_mfma(d)) ? 1 : 0
+
+extern "C" int pdeinv_realnvp_map_path(const pdeinv_realnvp_desc* d, int32_t impl) {
+  NVP_MAP_PATH(d, impl, "realnvp_map_path", path);
+  return path;
+}
+
+extern "C" int pdeinv_realnvp_map(const pdeinv_realnvp_desc* d, const float* params, const float* t, int64_t t_stride,
+                                  const float* x, int64_t n, int64_t ld, int32_t reverse, int32_t impl, float* y,
+                                  int64_t ld_y, float* ldj, float* logp, void* stream) {
+  NVP_MAP_PATH(d, impl, "realnvp_map", path);
+  PDEINV_REQUIRE(reverse == 0 || reverse == 1, PDEINV_ERR_INVALID, "realnvp_map: reverse must be 0 or 1");
+  if (ld_y == 0) ld_y = d->dim;
+  PDEINV_REQUIRE(n >= 0 && ld >= d->dim && ld_y >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID,
+                 "realnvp_map: bad sizes (n >= 0, ld_x >= dim, ld_y >= dim or 0, t_stride >= 0)");
+  PDEINV_REQUIRE(n <= (int64_t)0x7FFFFFFF * 128, PDEINV_ERR_INVALID, "realnvp_map: too many samples");
+  PDEINV_REQUIRE((((uintptr_t)params | (uintptr_t)t | (uintptr_t)x | (uintptr_t)y | (uintptr_t)ldj | (uintptr_t)logp) & 3) == 0,
+                 PDEINV_ERR_INVALID, "realnvp_map: misaligned pointer (4 bytes)");
+  if (n == 0) return PDEINV_OK;
+  PDEINV_REQUIRE(y || ldj || logp, PDEINV_ERR_INVALID, "realnvp_map: no output requested (d_y, d_ldj, d_logp all null)");
+  PDEINV_REQUIRE(params && t && x, PDEINV_ERR_INVALID, "realnvp_map: null device pointer");
+  const int D = d->dim;
+  const NvpArgs a = nvp_args(d);
+  const int64_t ls = layer_params(D, a.in_dim);
+  hipStream_t st = (hipStream_t)stream;
+  if (path == 1) {
+    const dim3 g(grid_for(n, kNvMapSPB));
+    const int y_vec = y && ld_y % 4 == 0 && ((uintptr_t)y & 15) == 0 ? 1 : 0;
+#define MAPK(PKK, RR) hipLaunchKernelGGL((realnvp_map_mfma_kernel<PKK, RR>), g, dim3(kBlock), 0, st, a, D, params, t, t_stride, x, n, ld, ls, y, ld_y, y_vec, ldj, logp)
+    if (nvp_packed(d)) {
+      if (reverse) MAPK(true, 1); else MAPK(true, 0);
+    } else {
+      if (reverse) MAPK(false, 1); else MAPK(false, 0);
+    }
+#undef MAPK
+    return check_launch("realnvp_map_mfma_kernel");
+  }
+  const dim3 g(grid_for(n));
+#define CASE(DD, RR) case DD: hipLaunchKernelGGL((realnvp_map_kernel<DD, RR>), g, dim3(kBlock), 0, st, a, params, t, t_stride, x, n, ld, ls, y, ld_y, ldj, logp); break;
+#define DIMS(RR) switch (D) { CASE(1, RR) CASE(2, RR) CASE(3, RR) CASE(4, RR) CASE(5, RR) CASE(6, RR) CASE(7, RR) CASE(8, RR) }
+  if (reverse) { DIMS(1) } else { DIMS(0) }
+#undef DIMS
+#undef CASE
+  return check_launch("realnvp_map_kernel");
 }

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "pdeinv_sde_simulate_mlp_supported", "pdeinv_sde_simulate_mlp_workspace_bytes", "pdeinv_sde_simulate_mlp",
     "pdeinv_mf_mlp_supported", "pdeinv_mf_mlp_workspace_bytes", "pdeinv_mf_mlp_prepare", "pdeinv_mf_mlp_force",
     "pdeinv_mf_mlp_step",
+    "pdeinv_realnvp_map_path", "pdeinv_realnvp_map",
 )
 
 
@@ -219,6 +220,8 @@ def lib():
         "pdeinv_realnvp_time_derivs": (i32, [P, P, P, i64, P, i64, i64, P, P, P]),
         "pdeinv_realnvp_time_derivs_sets": (i32, [P, P, P, P, i64, i64, i64, i64, P, P, P]),
         "pdeinv_realnvp_time_impl": (i32, [P, i32]),
+        "pdeinv_realnvp_map_path": (i32, [P, i32]),
+        "pdeinv_realnvp_map": (i32, [P, P, P, i64, P, i64, i64, i32, i32, P, i64, P, P, P]),
         "pdeinv_kmv_weights_from_ds_workspace_bytes": (ctypes.c_size_t, [i64, i64, i32]),
         "pdeinv_kmv_weights_from_ds": (i32, [i32, f32, P, P, i64, i64, i64, i64, P, P, P]),
         "pdeinv_realnvp_grad_workspace": (i64, [P, i64]),
@@ -1247,6 +1250,62 @@ def realnvp_time_impl(desc, impl: int = -1) -> str:
     if p < 0:
         raise NotImplementedError("RealNVP time derivatives: the matrix-core path does not take this flow")
     return NVP_TIME_PATHS[p]
+
+
+NVP_MAP_IMPLS = {"auto": NVP_TIME_AUTO, "general": NVP_TIME_GENERAL, "matrix": NVP_TIME_MATRIX}
+NVP_MAP_PATHS = {0: "general", 1: "matrix"}
+
+
+def _map_impl(impl) -> int:
+    if isinstance(impl, str):
+        if impl not in NVP_MAP_IMPLS:
+            raise ValueError(f"RealNVP map: impl must be one of {sorted(NVP_MAP_IMPLS)}")
+        return NVP_MAP_IMPLS[impl]
+    return int(impl)
+
+
+def realnvp_map_path(desc, impl="auto") -> str:
+    """The path realnvp_map takes for `desc` under `impl` ("auto" / "general" / "matrix"): "general" or "matrix"
+    (pdeinv_realnvp_map_path; stateless, no device call)."""
+    rc = int(lib().pdeinv_realnvp_map_path(ctypes.byref(desc) if desc is not None else None, _map_impl(impl)))
+    _check(min(rc, 0), "pdeinv_realnvp_map_path")
+    return NVP_MAP_PATHS[rc]
+
+
+def realnvp_map(desc, params: torch.Tensor, t: torch.Tensor, x: torch.Tensor, reverse, impl="auto", out=None,
+                want=("y", "ldj", "logp")):
+    """The flow as a map (pdeinv_realnvp_map) over rows x [n, dim] (a strided row view is honoured) and times t [n]
+    (or a single t, broadcast): reverse = 1 / True is the likelihood direction (data -> latent), 0 / False generates
+    (latent -> data at time t). Returns {"y": [n, dim], "ldj": [n], "logp": [n]} restricted to `want`; logp is the
+    flow's log-density of the point in data space. `out`: a [n, dim] row view (unit inner stride) to write y into;
+    `x` itself (same view) is allowed."""
+    _require_gpu()
+    n = x.shape[0]
+    _time_derivs_params(desc, params)
+    want = tuple(want)
+    if not want or any(w not in ("y", "ldj", "logp") for w in want):
+        raise ValueError("RealNVP map: want must name at least one of 'y', 'ldj', 'logp'")
+    t = t.reshape(-1)
+    if t.numel() not in (1, n):
+        raise ValueError("RealNVP: t must have one entry per row or a single entry")
+    px, _, ld = _rows(x, "x", desc.dim)
+    res, py, ld_y = {}, None, 0
+    if "y" in want or out is not None:
+        if out is None:
+            out = torch.empty((n, desc.dim), device=x.device, dtype=torch.float32)
+        py, ny, ld_y = _rows(out, "out", desc.dim)
+        if ny != n:
+            raise ValueError(f"RealNVP map: out must have {n} rows")
+        res["y"] = out
+    for k in ("ldj", "logp"):
+        if k in want:
+            res[k] = torch.empty(n, device=x.device, dtype=torch.float32)
+    t = t.contiguous()
+    _check(lib().pdeinv_realnvp_map(ctypes.byref(desc), _dev(params, "params"), _dev(t, "t"),
+                                    0 if t.numel() == 1 else 1, px, n, ld, int(bool(reverse)), _map_impl(impl), py,
+                                    ld_y, _dev(res.get("ldj"), "ldj"), _dev(res.get("logp"), "logp"),
+                                    stream_handle()), "pdeinv_realnvp_map")
+    return res
 
 
 def _time_derivs_params(desc, params: torch.Tensor) -> None:
