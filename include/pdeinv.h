@@ -51,7 +51,8 @@ extern "C" {
  * PDEINV_POT_MLP, pdeinv_mlp_shape, pdeinv_mlp_potential(_path, _workspace_bytes),
  * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes); PDEINV_POT_MEANFIELD_MLP,
  * pdeinv_mf_mlp_supported, pdeinv_mf_mlp_workspace_bytes, pdeinv_mf_mlp_prepare, pdeinv_mf_mlp_force,
- * pdeinv_mf_mlp_step; pdeinv_realnvp_map, pdeinv_realnvp_map_path (additive as well: the version stays 10). */
+ * pdeinv_mf_mlp_step; pdeinv_realnvp_map, pdeinv_realnvp_map_path; pdeinv_realnvp_score,
+ * pdeinv_realnvp_score_path, pdeinv_realnvp_score_workspace_bytes (additive as well: the version stays 10). */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -739,6 +740,27 @@ int pdeinv_realnvp_map_path(const pdeinv_realnvp_desc* desc, int32_t impl);
 int pdeinv_realnvp_map(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_t, int64_t t_stride,
                        const float* d_x, int64_t n, int64_t ld_x, int32_t reverse, int32_t impl, float* d_y,
                        int64_t ld_y, float* d_ldj, float* d_logp, void* stream);
+
+/* The score of the flow's density: d_score[i * ld_s + k] = d log p_{t_i}(x_i) / d x_k (k < dim; floats of a row
+ * beyond dim are not written; ld_s == 0: dim) and, optionally, d_logp[i] = log p_{t_i}(x_i), by reverse mode per
+ * sample: the likelihood pass of pdeinv_realnvp_map(reverse = 1), then the adjoint g = -Sigma^-1 (x0 - mu) of the base
+ * density carried back through the coupling layers. Kinked activations (relu, celu / elu at 0) take the derivative
+ * of the branch taken. Each layer's input is kept from the likelihood pass in d_workspace
+ * (pdeinv_realnvp_score_workspace_bytes: n_layers * dim * n floats on the general path), not rebuilt by inverting
+ * the layer, which would cost 7 - 8 x in accuracy on stiff flows. d_score and d_logp are each nullable (at least one
+ * must be given); with d_score null no workspace is needed. t_stride 0 broadcasts d_t[0]. n == 0 is a no-op. Plain
+ * stores, no atomics: a sample's outputs depend on its row, its t and the parameters only (not on n or its
+ * position). Stream-ordered. impl: PDEINV_NVP_TIME_AUTO / _GENERAL / _MATRIX, per call (the workspace size depends
+ * on it: ask with the impl of the call). The general path (one thread per sample) takes the whole descriptor
+ * envelope; the matrix-core path takes celu / elu flows (any dim <= 8, any E, ignore_time), else UNSUPPORTED. AUTO
+ * takes the matrix-core path only where it measured faster. All argument checks run before any device call.
+ * pdeinv_realnvp_score_path: the path `desc` takes under `impl`: 0 general, 1 matrix-core, or a negative status;
+ * stateless, no device call. */
+int pdeinv_realnvp_score_path(const pdeinv_realnvp_desc* desc, int32_t impl);
+size_t pdeinv_realnvp_score_workspace_bytes(const pdeinv_realnvp_desc* desc, int64_t n, int32_t impl);
+int pdeinv_realnvp_score(const pdeinv_realnvp_desc* desc, const float* d_params, const float* d_t, int64_t t_stride,
+                         const float* d_x, int64_t n, int64_t ld_x, int32_t impl, float* d_score, int64_t ld_s,
+                         float* d_logp, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* Maximum-likelihood value_and_grad of the flow (replaces jax.value_and_grad(loss_fn) in
  * core/log_density_estimation.py:47-58): *d_loss = -mean_i log p_{t_i}(x_i), d_grad[param_count]

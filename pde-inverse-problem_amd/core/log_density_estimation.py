@@ -11,7 +11,8 @@ jax.value_and_grad) and takes an Adam step (b1 = 0.9, eps = 1e-4) on the fused n
 with the reference's constant / cosine / constant learning-rate schedule (:116-145). Epoch losses
 stay on the device and are fetched once per print interval. The closing density plot
 (plot_trajectory_of_distributions, matplotlib + wandb) is out of scope; `flow_moment_error` is its numeric
-stand-in (moments of flow samples against the data's, per time stamp).
+stand-in (moments of flow samples against the data's, per time stamp); where the true marginal is a known Gaussian,
+`flow_divergence` measures the fit itself: the KL and the relative Fisher divergence of the learned density from it.
 """
 from __future__ import annotations
 
@@ -54,7 +55,7 @@ def create_custom_schedule(lr, T0, T1):
 def make_log_density_fn(model: RealNVP, params):
     """log_density_fn(t, x) of a flow and its parameters, as estimate_log_density returns it: .model, .params and
     .partial_s(t, x) -> (ds log p, ds2 log p) (pdeinv_realnvp_time_derivs), .sample(key, t, n) -> (x, log p) and
-    .inverse(t, x) -> (x0, ldj) (pdeinv_realnvp_map)."""
+    .inverse(t, x) -> (x0, ldj) (pdeinv_realnvp_map), .score(t, x) -> grad_x log p (pdeinv_realnvp_score)."""
     def log_density_fn(t, x):
         return model.apply(params, t, x)
 
@@ -67,6 +68,7 @@ def make_log_density_fn(model: RealNVP, params):
     log_density_fn.partial_s = partial_s
     log_density_fn.sample = lambda key, t, n, **kw: model.sample(params, key, t, n, **kw)
     log_density_fn.inverse = lambda t, x: model.inverse(params, t, x)
+    log_density_fn.score = lambda t, x: model.score(params, t, x)
     return log_density_fn
 
 
@@ -114,6 +116,48 @@ def flow_moment_error(log_density_fn, key, dataset, time_index, n_per_time):
     err_mean = torch.linalg.vector_norm(m_f - m_d, dim=-1) / torch.linalg.vector_norm(m_d, dim=-1)
     err_cov = torch.linalg.matrix_norm(c_f - c_d) / torch.linalg.matrix_norm(c_d)
     return err_mean, err_cov
+
+
+def flow_divergence_from_gaussian(log_density_fn, key, taus, mean, cov, n_per_time, row_offset=0, counter_offset=0):
+    """Divergences of the learned density rho^_t from a known Gaussian truth rho_t = N(mean_k, cov_k) per time stamp
+    taus[k] (what the reference's test_fn meant to report as "KL" and "Fisher Information"), estimated on n_per_time
+    draws x of the truth per stamp:
+      kl[k]         = mean[log rho(x) - log rho^(x)]                                   (KL(rho || rho^))
+      fisher_rel[k] = mean|grad log rho^(x) + P^-1 (x - m)|^2 / mean|P^-1 (x - m)|^2   (relative Fisher divergence)
+    The rows: native.gaussian_sample_grouped(n_per_time, mean as fp32, the lower Cholesky factors of cov as fp32,
+    seed=key.seed, counter_offset=counter_offset, row_offset=row_offset), the seed taken from `key` as
+    Gaussian.sample takes it, so a caller can redraw them; stamp k owns rows k * n_per_time .. (k + 1) * n_per_time.
+    One native.realnvp_score call over all stamps with t repeated gives log rho^ and its score; the truth's terms
+    and the means are formed in fp64 on the device. mean [n_t, d] and cov [n_t, d, d]: host fp64. Returns
+    (kl [n_t], fisher_rel [n_t]) as fp64 device tensors."""
+    model = log_density_fn.model
+    d = model.mnf.dim
+    flat = log_density_fn.params["params"]
+    dev = flat.device
+    taus = torch.as_tensor(taus, dtype=torch.float32, device=dev).reshape(-1)
+    n_t, n = taus.numel(), int(n_per_time)
+    mean = np.asarray(mean, dtype=np.float64).reshape(n_t, d)
+    cov = np.asarray(cov, dtype=np.float64).reshape(n_t, d, d)
+    half = np.linalg.cholesky(cov)
+    x = native.gaussian_sample_grouped(n, torch.as_tensor(mean, dtype=torch.float32, device=dev),
+                                       torch.as_tensor(half, dtype=torch.float32, device=dev), seed=key.seed,
+                                       counter_offset=counter_offset, row_offset=row_offset)
+    res = native.realnvp_score(model._desc, flat, taus.repeat_interleave(n), x)
+    P_inv = torch.as_tensor(np.linalg.inv(cov), device=dev)                               # [n_t, d, d] fp64
+    log_norm = torch.as_tensor(np.linalg.slogdet(2 * np.pi * cov)[1], device=dev)         # [n_t]
+    off = x.double().reshape(n_t, n, d) - torch.as_tensor(mean, device=dev)[:, None, :]
+    w = torch.einsum("kij,knj->kni", P_inv, off)                                          # -grad log rho
+    logp_true = -0.5 * (log_norm[:, None] + (off * w).sum(-1))
+    kl = (logp_true - res["logp"].double().reshape(n_t, n)).mean(1)
+    num = ((res["score"].double().reshape(n_t, n, d) + w) ** 2).sum(-1).mean(1)
+    return kl, num / (w ** 2).sum(-1).mean(1)
+
+
+def flow_divergence(log_density_fn, key, pde_instance, taus, n_per_time):
+    """flow_divergence_from_gaussian against the instance's closed-form X-marginal (pde_instance.x_marginal, the
+    OU / McKean-Vlasov problems): (kl [n_t], fisher_rel [n_t]) of the learned density per time stamp."""
+    mean, cov = pde_instance.x_marginal(np.asarray(torch.as_tensor(taus).detach().cpu(), dtype=np.float64).reshape(-1))
+    return flow_divergence_from_gaussian(log_density_fn, key, taus, mean, cov, n_per_time)
 
 
 def estimate_log_density(cfg, pde_instance, rng, num_epochs: int = 20000, frequency: int = 100, verbose=True,

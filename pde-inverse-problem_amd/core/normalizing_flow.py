@@ -5,7 +5,8 @@ Same constructor arguments and call convention as the reference's flax modules:
 `RealNVP(mnf, log_prob_0)`; `init(key, t, x) -> params`, `apply(params, t, x) -> log p_t(x)` for a
 single (t, x) or batched rows (the reference vmaps the same call). The evaluation is the HIP
 kernel `pdeinv_realnvp_logdensity` (one thread per sample, VALU); `MNF.apply(params, t, x, reverse)` is the flow
-as a two-way map (`pdeinv_realnvp_map`), with `RealNVP.inverse / forward / sample` on it; params are a flat fp32 device
+as a two-way map (`pdeinv_realnvp_map`), with `RealNVP.inverse / forward / sample` on it; `RealNVP.score` is
+grad_x log p_t(x) (`pdeinv_realnvp_score`); params are a flat fp32 device
 vector in the layout documented in include/pdeinv.h. `log_prob_0` must be a `core.distribution.Gaussian`
 (the reference passes `distribution_initial_x.logdensity`, log_density_estimation.py:22).
 """
@@ -183,6 +184,17 @@ class RealNVP:
         if single:
             return logp[0], ds[0, 0], ds[0, 1]
         return logp, ds[:, 0], ds[:, 1]
+
+    def score(self, params, t, x):
+        """grad_x log p_t(x), what jax.grad(log_density_fn, 1) gives in the reference, by reverse mode on the HIP
+        kernel `pdeinv_realnvp_score`. Unbatched / batched like `apply`."""
+        flat = params["params"] if isinstance(params, dict) else params
+        x = torch.as_tensor(x, dtype=torch.float32, device=flat.device)
+        single = x.dim() == 1
+        rows = x.reshape(1, -1) if single else x
+        tt = torch.as_tensor(t, dtype=torch.float32, device=flat.device).reshape(-1)
+        out = native.realnvp_score(self._desc, flat, tt, rows, want=("score",))["score"]
+        return out[0] if single else out
 
     def value_and_grad(self, params, t, x):
         """(loss, grad) with loss = -mean_i log p_{t_i}(x_i) and grad flat like params

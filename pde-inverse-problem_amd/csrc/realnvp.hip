@@ -1,4 +1,4 @@
-// realnvp.hip — the time-conditioned RealNVP flow (core/normalizing_flow.py:8-229) in four parts:
+// realnvp.hip — the time-conditioned RealNVP flow (core/normalizing_flow.py:8-229) in five parts:
 //  1. realnvp_logdensity_kernel: log p_t(x), one thread per (t, x) sample, the tiny MLPs (widths 8 / 16 / 16,
 //     SURVEY.md §8(a) a12) in VGPRs on the VALU, weights at wave-uniform addresses (scalar loads). Helpers:
 //     nvp_act, dense, basic_mlp.
@@ -11,8 +11,12 @@
 //  4. The flow as a map in either direction (y, ldj, log p; pdeinv_realnvp_map): realnvp_map_kernel (general, one
 //     thread per sample, part 1's arithmetic over a compile-time direction) and realnvp_map_mfma_kernel (matrix
 //     cores: part 2's likelihood pass on its tile machinery, run forwards or backwards through the layers).
+//  5. The score grad_x log p (pdeinv_realnvp_score), reverse mode with each layer's input kept in a workspace:
+//     realnvp_score_kernel (general, one thread per sample; helpers nvp_dense_d1, nvp_mlp_d1, nvp_mlp_bwd_x on part
+//     3's nvp_act_d2) and realnvp_score_mfma_kernel (matrix cores: part 2's likelihood pass and backward sweep without
+//     its weight gradients; helper nv_mlp_bwd_in); nvp_couple1 is the coupling update of both, in both passes.
 // Shared: NvpArgs (masks and the base Gaussian travel in the kernel arguments) and nvp_temb_params by all;
-// the block-level staging nv_lane / nv_stage_* by the three tile kernels; the three-stream arithmetic nvp_act3,
+// the block-level staging nv_lane / nv_stage_* by the four tile kernels; the three-stream arithmetic nvp_act3,
 // NVP_COUPLE3 and NVP_BASE_STORE3 (macros: see there) by the two time kernels; one descriptor
 // check (NVP_REQUIRE_DESC) and one NvpArgs fill (nvp_args) by the host entry points.
 // Still written twice, on purpose: the time embedding's forward (sinusoid, bias, nv_fwdT, celu) in
@@ -1848,6 +1852,546 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void real
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The score grad_x log p_t(x) (pdeinv_realnvp_score), reverse mode per sample.
+// Likelihood pass, layers l = L-1 .. 0 (m the mask, k = 1 - m, c = t under the hard parameterisation, else 1):
+//   s = tanh(c s^ / f) f k, f = e^alpha;  tau = c tau^ k;  x <- (x + tau) e^s;  ldj += sum s
+// then log p = log p0(x0) + ldj and the adjoint starts as g = -Sigma^-1 (x0 - mu). Backward sweep, l = 0 .. L-1,
+// with x_out the layer's output and x_in its input:
+//   gs = (g x_out + 1) k;  s^bar = c gs (1 - tanh^2);  tau^bar = c g e^s k
+//   g <- g e^s + m (J_s^T s^bar + J_tau^T tau^bar)[:dim]
+// and after layer L-1 g is the score. Kinked activations take the derivative of the branch taken.
+// Each layer's input is kept, not rebuilt by inverting the layer (x_out e^{-s} - tau loses 7 - 8 x on stiff flows):
+// the likelihood pass writes the coordinates the layer changes (mask 0) into the caller's workspace, [L][D][n]
+// floats (sample innermost: a wave's stores and loads are one run), and the sweep reads them back. Its nets then
+// see the bits the likelihood pass saw, so s, e^s and tau are that pass's.
+// General path: one thread per sample on the VALU like realnvp_time_kernel (weights at wave-uniform addresses, ACT
+// a template parameter, register arrays indexed by unrolled counters only); the nets keep g' of their three hidden
+// layers (from nvp_act_d2, with the value) for the transposed sweep. Accurate expf / tanhf / division in the
+// coupling, NvFreq frequencies. Plain stores, no atomics: deterministic.
+// ---------------------------------------------------------------------------------------------
+// out = g(b + [in0 | in1] @ W), d1 = g' there: rows of in0 (N0, all), then of in1 (rows i < n1 of N1)
+template <int ACT, int N0, int N1, int NO>
+__device__ __forceinline__ const float* nvp_dense_d1(const float* __restrict__ W, const float (&in0)[N0],
+                                                     const float (&in1)[N1], int n1, float (&out)[NO],
+                                                     float (&d1)[NO]) {
+  asm volatile("" ::: "memory");  // no weight fetches hoisted across dense layers (register pressure)
+  const float* b = W + (N0 + n1) * NO;
+#pragma unroll
+  for (int o = 0; o < NO; ++o) out[o] = b[o];
+#pragma unroll
+  for (int i = 0; i < N0; ++i)
+#pragma unroll
+    for (int o = 0; o < NO; ++o) out[o] = fmaf(in0[i], W[i * NO + o], out[o]);
+#pragma unroll
+  for (int i = 0; i < N1; ++i) {
+    if (i < n1) {
+#pragma unroll
+      for (int o = 0; o < NO; ++o) out[o] = fmaf(in1[i], W[(N0 + i) * NO + o], out[o]);
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    float g, g1, g2;
+    nvp_act_d2<ACT>(out[o], g, g1, g2);
+    out[o] = g;
+    d1[o] = g1;
+  }
+  return b + NO;
+}
+
+// BasicMLP over [xm (D) | temb (n_t)]: its output and g' of the three hidden layers
+template <int D, int ACT>
+__device__ __forceinline__ const float* nvp_mlp_d1(const float* p, const float (&xm)[D], const float (&temb)[16],
+                                                   int n_t, float (&out)[D], float (&a0)[8], float (&a1)[16],
+                                                   float (&a2)[16]) {
+  float h0[8], h1[16], h2[16];
+  const float none[1] = {0.f};
+  p = nvp_dense_d1<ACT, D, 16, 8>(p, xm, temb, n_t, h0, a0);
+  p = nvp_dense_d1<ACT, 8, 1, 16>(p, h0, none, 0, h1, a1);
+  p = nvp_dense_d1<ACT, 16, 1, 16>(p, h1, none, 0, h2, a2);
+  asm volatile("" ::: "memory");
+  const float* b = p + 16 * D;
+#pragma unroll
+  for (int k = 0; k < D; ++k) out[k] = b[k];
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+#pragma unroll
+    for (int k = 0; k < D; ++k) out[k] = fmaf(h2[i], p[i * D + k], out[k]);
+  return b + D;
+}
+
+// gin += (d out / d xm)^T dout of the BasicMLP at p (n_in = D + n_t input rows), from the g' nvp_mlp_d1 kept
+template <int D>
+__device__ __forceinline__ void nvp_mlp_bwd_x(const float* p, int n_in, const float (&dout)[D], const float (&a0)[8],
+                                              const float (&a1)[16], const float (&a2)[16], float (&gin)[D]) {
+  const float* W0 = p;
+  const float* W1 = W0 + n_in * 8 + 8;
+  const float* W2 = W1 + 8 * 16 + 16;
+  const float* W3 = W2 + 16 * 16 + 16;
+  float d2[16], d1[16], d0[8];
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc = fmaf(W3[i * D + k], dout[k], acc);
+    d2[i] = acc * a2[i];
+  }
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < 16; ++o) acc = fmaf(W2[i * 16 + o], d2[o], acc);
+    d1[i] = acc * a1[i];
+  }
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int o = 0; o < 16; ++o) acc = fmaf(W1[i * 16 + o], d1[o], acc);
+    d0[i] = acc * a0[i];
+  }
+  asm volatile("" ::: "memory");
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    float acc = gin[k];
+#pragma unroll
+    for (int o = 0; o < 8; ++o) acc = fmaf(W0[k * 8 + o], d0[o], acc);
+    gin[k] = acc;
+  }
+}
+
+// One coordinate's coupling terms, the value stream of NVP_COUPLE3: th = tanh(c s^ / f), sk = th f k, es = e^{sk},
+// tk = c tau^ k; both passes of the score kernel go through here, so the sweep's are the likelihood pass's bits.
+__device__ __forceinline__ void nvp_couple1(float t, bool hard, float sf, float keep, float s, float tr, float& th,
+                                            float& sk, float& es, float& tk) {
+  if (hard) {
+    s *= t;
+    tr *= t;
+  }
+  th = tanhf(s / sf);
+  sk = th * sf * keep;
+  es = expf(sk);
+  tk = tr * keep;
+}
+
+// score rows [n, D] at stride ld_s (nullable: log p only, no workspace traffic), logp nullable; ws: [L][D][n] floats.
+template <int D, int ACT>
+__global__ __launch_bounds__(kBlock, 2) void realnvp_score_kernel(NvpArgs a, NvFreq fr, const float* __restrict__ params,
+                                                               const float* __restrict__ tv, int64_t t_stride,
+                                                               const float* __restrict__ xv, int64_t n, int64_t ld,
+                                                               int64_t layer_stride, float* __restrict__ score,
+                                                               int64_t ld_s, float* __restrict__ logp,
+                                                               float* __restrict__ ws) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const float t = tv[i * t_stride];
+  float x[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[k] = xv[i * ld + k];
+  float temb[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) temb[q] = 0.f;
+  const float* p = params;
+  const int E = a.E;
+  if (!a.ignore_time) {
+    if (E > 0) {
+      const int half = E / 2;
+      float se[16], h[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {  // position q: sin of frequency q (q < half), cos of frequency q - half
+        se[q] = 0.f;
+        if (q < E) {
+          float sn, cs;
+          sincosf(t * fr.w[q], &sn, &cs);
+          se[q] = q < half ? sn : cs;
+        }
+      }
+      // two E x E dense layers, unrolled to 16 x 16 with the rows and columns >= E skipped
+      auto layer = [&](const float* W, const float (&in)[16], float (&out)[16]) {
+#pragma unroll
+        for (int o = 0; o < 16; ++o) out[o] = o < E ? W[E * E + o] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          if (q < E) {
+#pragma unroll
+            for (int o = 0; o < 16; ++o)
+              if (o < E) out[o] = fmaf(in[q], W[q * E + o], out[o]);
+          }
+        }
+      };
+      layer(p, se, h);
+#pragma unroll
+      for (int o = 0; o < 16; ++o) {
+        if (o < E) {
+          float g, g1, g2;
+          nvp_act_d2<ACT>(h[o], g, g1, g2);
+          h[o] = g;
+        }
+      }
+      p += E * E + E;
+      layer(p, h, temb);
+      p += E * E + E;
+    } else {
+      temb[0] = t;
+    }
+  }
+  const float* layers = p;
+  const bool hard = !a.ignore_time && a.soft_init == 0.f;
+  const int n_t = a.in_dim - D;
+  float ldj = 0.f;
+  for (int l = a.n_layers - 1; l >= 0; --l) {  // likelihood direction: reversed layers
+    const float* lp = layers + (int64_t)l * layer_stride;
+    const float* m = a.masks + l * D;
+    float xm[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      xm[k] = x[k] * m[k];
+      if (score && m[k] == 0.f) ws[((int64_t)l * D + k) * n + i] = x[k];  // the layer's input, where it changes
+    }
+    float sc[D], tr[D], a0[8], a1[16], a2[16];
+    const float* q = nvp_mlp_d1<D, ACT>(lp + D, xm, temb, n_t, sc, a0, a1, a2);
+    nvp_mlp_d1<D, ACT>(q, xm, temb, n_t, tr, a0, a1, a2);
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      float th, sk, es, tk;
+      nvp_couple1(t, hard, expf(lp[k]), 1.f - m[k], sc[k], tr[k], th, sk, es, tk);
+      x[k] = (x[k] + tk) * es;
+      ldj += sk;
+    }
+  }
+  // base density; its gradient -1/2 (A + A^T) (x0 - mean) (A need not be symmetric)
+  float g[D];
+  {
+    float diff[D], quad = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) diff[k] = x[k] - a.mean[k];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      float acc = 0.f, accT = 0.f;
+#pragma unroll
+      for (int c = 0; c < D; ++c) {
+        acc = fmaf(a.inv_cov[r * D + c], diff[c], acc);
+        accT = fmaf(a.inv_cov[c * D + r], diff[c], accT);
+      }
+      quad = fmaf(diff[r], acc, quad);
+      g[r] = -0.5f * (acc + accT);
+    }
+    if (logp) logp[i] = -0.5f * (a.log_det + quad) + ldj;
+  }
+  if (!score) return;
+  for (int l = 0; l < a.n_layers; ++l) {  // backward sweep: x is layer l's output on entry, its input on exit
+    const float* lp = layers + (int64_t)l * layer_stride;
+    const float* m = a.masks + l * D;
+    float xin[D], xm[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      xin[k] = m[k] == 0.f ? ws[((int64_t)l * D + k) * n + i] : x[k];
+      xm[k] = xin[k] * m[k];
+    }
+    float sc[D], tr[D], s0[8], s1[16], s2[16], t0[8], t1[16], t2[16];
+    const float* q = nvp_mlp_d1<D, ACT>(lp + D, xm, temb, n_t, sc, s0, s1, s2);
+    nvp_mlp_d1<D, ACT>(q, xm, temb, n_t, tr, t0, t1, t2);
+    float sbar[D], tbar[D], gnet[D];
+    const float c = hard ? t : 1.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const float keep = 1.f - m[k];
+      float th, sk, es, tk;
+      nvp_couple1(t, hard, expf(lp[k]), keep, sc[k], tr[k], th, sk, es, tk);
+      const float gs = fmaf(g[k], x[k], 1.f) * keep;
+      sbar[k] = c * gs * (1.f - th * th);
+      tbar[k] = c * g[k] * es * keep;
+      g[k] *= es;
+      gnet[k] = 0.f;
+      x[k] = xin[k];
+    }
+    nvp_mlp_bwd_x<D>(lp + D, a.in_dim, sbar, s0, s1, s2, gnet);
+    nvp_mlp_bwd_x<D>(q, a.in_dim, tbar, t0, t1, t2, gnet);
+#pragma unroll
+    for (int k = 0; k < D; ++k) g[k] = fmaf(m[k], gnet[k], g[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) score[i * ld_s + k] = g[k];
+}
+
+// ---------------------------------------------------------------------------------------------
+// The score on the matrix cores (pdeinv_realnvp_score's matrix-core path; celu / elu, either layout): the likelihood
+// pass and the backward sweep of realnvp_grad_kernel on its tile machinery, without that kernel's weight-gradient
+// products, accumulators, sample stage, slab, flush and reduce. Layers staged through the nv_layer_dst table with
+// their transposed copies (2 L stagings: L-1 .. 0, then 0 .. L-1), nets through nv_mlp_fwd<PK>, their transposed
+// sweep through nv_mlp_bwd_in<PK> (the input-gradient half of nv_mlp_bwd). The coupling terms are nvp_couple1's
+// (accurate expf / tanhf / division), in both passes. Kept inputs: per layer and coordinate register the wave's
+// tile as it sits in the lanes, [L][NC][tiles of 16 samples][64 lanes] floats (one 256-byte run per wave store and
+// load); only the lanes whose coordinate the layer changes (mask 0) write and read. Base form and its gradient:
+// every lane gathers its sample's coordinates from the owning lanes (__shfl), as the map kernel does. Stores: the
+// owning lanes write the score as the map kernel writes y, lane group 0 logp. Plain stores, no atomics.
+// ---------------------------------------------------------------------------------------------
+constexpr int kNvWavesScorePk = 4;  // waves per SIMD, packed layout
+constexpr int kNvWavesScore = 3;    // waves per SIMD, identity layout
+
+// The input-gradient half of nv_mlp_bwd: gx += (d out / d xm)^T dout, from the forward's activations h
+template <bool PK>
+__device__ __forceinline__ void nv_mlp_bwd_in(const float* p, const NvLane& ln, const NvAct& h, const NvV& dout,
+                                              NvV& gx) {
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  NvV d, e;
+  nv_bcast(e, z4);
+  nv_fwdT<PK ? 0x1 : 0xF>(p + NvM<PK>::TR + NvM<PK>::W3, ln, dout, e);
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) d[u] = nv_dact4(e[u], h.h2[u]);
+  nv_bcast(e, z4);
+  nv_fwdT(p + NvM<PK>::TR + NvM<PK>::W2, ln, d, e);
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) d[u] = nv_dact4(e[u], h.h1[u]);
+  nv_bcast(e, z4);
+  nv_fwdT(p + NvM<PK>::TR + NvM<PK>::W1, ln, d, e);
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    if constexpr (PK)  // registers 2, 3: padding units
+      d[u] = f32x4{e[u][0] * nvp_celu_grad_h(h.h0[u][0]), e[u][1] * nvp_celu_grad_h(h.h0[u][1]), 0.f, 0.f};
+    else
+      d[u] = nv_dact4(e[u], h.h0[u]);
+  }
+  if constexpr (PK) {
+    nv_bcast(e, z4);
+    nv_fwdT<0x3>(p + NvM<PK>::TR + NvM<PK>::W0T, ln, d, e);
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) gx[u][0] += e[u][0];
+  } else {
+    nv_fwdT(p + NvM<PK>::TR + NvM<PK>::W0X, ln, d, gx);
+  }
+}
+
+// ws: [L][NC][n_tiles][64] floats, n_tiles = ceil(n / 16) (pdeinv_realnvp_score_workspace_bytes)
+template <bool PK>
+__global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void realnvp_score_mfma_kernel(
+    NvpArgs a, NvFreq fr, int d, const float* __restrict__ params, const float* __restrict__ tv, int64_t t_stride,
+    const float* __restrict__ xv, int64_t n, int64_t ld, int64_t layer_stride, float* __restrict__ score,
+    int64_t ld_s, int s_vec, float* __restrict__ logp_out, float* __restrict__ ws, int64_t n_tiles) {
+  using M = NvM<PK>;
+  constexpr int NC = PK ? 1 : 4;    // registers that hold coordinates
+  constexpr int DMAX = PK ? 4 : 8;  // coordinates a layout can hold
+  __shared__ float sW[M::LAYER];    // current coupling layer (padded, with transposes); the time embedding before the first
+  __shared__ float sF[48];          // sinusoid table: frequency, sin weight, cos weight
+  __shared__ float sB[16 * 8];      // symmetrised inverse covariance: rows by position, columns by coordinate
+  __shared__ uint32_t sDst[kNvRaw];
+  const int E = a.E, n_t = a.in_dim - d, L = a.n_layers;
+  const float* layers = params + nvp_temb_params(E);
+  const bool hard = !a.ignore_time && a.soft_init == 0.f;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const NvLane ln = nv_lane(tid, false);
+  nv_stage_sinusoid(sF, E, [&fr](int q) { return fr.w[q]; });
+  nv_stage_init<PK>(sDst, sW, layer_stride, d, n_t);
+  for (int q = tid; q < 16 * 8; q += kBlock) {
+    const int r = nv_xinv<PK>(q / 8, d), c = q % 8;
+    sB[q] = (r >= 0 && c < d) ? 0.5f * (a.inv_cov[r * d + c] + a.inv_cov[c * d + r]) : 0.f;
+  }
+  float pre[kNvPre];
+  auto prefetch = [&](int l) {
+    const float* lp = layers + (int64_t)l * layer_stride;
+#pragma unroll
+    for (int k = 0; k < kNvPre; ++k) {
+      const int q = tid + k * kBlock;
+      pre[k] = q < layer_stride ? lp[q] : 0.f;
+    }
+  };
+  int staged = 0;  // layers staged so far
+  auto stage_layer = [&](int l) {
+    __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
+    nv_stage_mask<PK>(sW, a, l, d);
+#pragma unroll
+    for (int k = 0; k < kNvPre; ++k) {
+      const int q = tid + k * kBlock;
+      if (q < layer_stride) {
+        const uint32_t t = sDst[q];
+        sW[t & 0xFFFFu] = pre[k];
+        if ((t >> 16) != 0xFFFFu) sW[t >> 16] = pre[k];
+      }
+    }
+    ++staged;
+    if (staged < 2 * L && (score || staged < L)) prefetch(staged < L ? L - 1 - staged : staged - L);
+    __syncthreads();
+  };
+  prefetch(L - 1);
+  __syncthreads();  // sW zeroed
+  if (E > 0) nv_stage_temb<PK>(sW, params, E, false);
+  __syncthreads();
+  // ---- the wave's tiles ----
+  NvV x, g, temb;
+  float tt[kNvT], ldj[kNvT];
+  const int64_t base = (int64_t)blockIdx.x * kNvSPB + wave * 16 * kNvT;
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    const int64_t i = base + 16 * u + ln.s;
+    const bool active = i < n;
+    tt[u] = active ? tv[i * t_stride] : 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int k = nv_xinv<PK>(4 * ln.g + c, d);
+      x[u][c] = (active && k >= 0 && (!PK || c == 0)) ? xv[i * ld + k] : 0.f;  // packed: registers 1..3 are 0
+    }
+    ldj[u] = 0.f;
+  }
+  if (E > 0) {  // TimeEmbedding (:8-22)
+    NvV se, he;
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int q = 4 * ln.g + c;
+        float sn, cs;
+        sincosf(tt[u] * sF[q], &sn, &cs);
+        se[u][c] = sF[16 + q] * sn + sF[32 + q] * cs;
+      }
+    nv_bcast(he, nv_vec(sW + M::E_B1, ln));
+    nv_fwdT(sW + M::E_W1, ln, se, he);
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
+    nv_bcast(temb, nv_vec(sW + M::E_B2, ln));
+    nv_fwdT(sW + M::E_W2, ln, he, temb);
+    __syncthreads();  // every wave has read the time embedding: back to the zero-padded layer image
+    for (int q = tid; q < M::TEMB; q += kBlock) sW[q] = 0.f;
+  } else {
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) temb[u][c] = (!a.ignore_time && 4 * ln.g + c == nv_tpos<PK>(0)) ? tt[u] : 0.f;
+  }
+  // the kept-input slot of (layer l, tile u, register c) for this lane; tiles past the batch have none
+  auto slot = [&](int l, int u, int c) { return (((int64_t)l * NC + c) * n_tiles + (base >> 4) + u) * 64 + lane; };
+  bool tile_in[kNvT];
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) tile_in[u] = (base >> 4) + u < n_tiles;
+  auto masked = [](const NvV& x, const f32x4& m, NvV& xm) {
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
+  };
+  // ---- likelihood pass (layers L-1 .. 0): x <- (x + tr) e^s ----
+  for (int l = L - 1; l >= 0; --l) {
+    stage_layer(l);
+    const f32x4 m = nv_vec(sW + M::MASK, ln);
+    const f32x4 sfw = nv_vec(sW + M::SF, ln);
+    NvV xm, so, to;
+    masked(x, m, xm);
+    {
+      NvAct h;
+      nv_mlp_fwd<PK>(sW + M::SNET, ln, temb, xm, h, so);
+      nv_mlp_fwd<PK>(sW + M::TNET, ln, temb, xm, h, to);
+    }
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {  // padded / masked coordinates: keep = 0, x unchanged
+        if (score && tile_in[u] && m[c] == 0.f) ws[slot(l, u, c)] = x[u][c];  // the layer's input, where it changes
+        float th, sk, es, tk;
+        nvp_couple1(tt[u], hard, expf(sfw[c]), 1.f - m[c], so[u][c], to[u][c], th, sk, es, tk);
+        x[u][c] = (x[u][c] + tk) * es;
+        ldj[u] += sk;
+      }
+    }
+  }
+  // ---- base density log p0(x0) and its gradient -1/2 (A + A^T) (x0 - mean) ----
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    float xc[DMAX];
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+      const float v = __shfl(PK ? x[u][0] : x[u][k & 3], 16 * (PK ? k : k >> 2) + ln.s, 64);
+      xc[k] = k < d ? v - a.mean[k] : 0.f;
+    }
+    float quad = 0.f;
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+      if (r < d) {
+        float acc = 0.f;
+#pragma unroll
+        for (int c = 0; c < DMAX; ++c)
+          if (c < d) acc = fmaf(a.inv_cov[r * d + c], xc[c], acc);
+        quad = fmaf(xc[r], acc, quad);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float acc = 0.f;
+      if (!PK || c == 0) {
+#pragma unroll
+        for (int q = 0; q < DMAX; ++q) acc = fmaf(sB[(4 * ln.g + c) * 8 + q], xc[q], acc);
+      }
+      g[u][c] = -acc;
+    }
+    float lj = ldj[u];  // the four lane groups' parts
+    lj += __shfl_xor(lj, 16, 64);
+    lj += __shfl_xor(lj, 32, 64);
+    const int64_t i = base + 16 * u + ln.s;
+    if (logp_out && i < n && ln.g == 0) logp_out[i] = -0.5f * (a.log_det + quad) + lj;
+  }
+  if (!score) return;  // block-uniform
+  // ---- backward sweep (layers 0 .. L-1): x is the layer's output on entry, its kept input on exit ----
+  for (int l = 0; l < L; ++l) {
+    stage_layer(l);
+    const f32x4 m = nv_vec(sW + M::MASK, ln);
+    const f32x4 sfw = nv_vec(sW + M::SF, ln);
+    NvV xin, xm, out, es, gso, gto, gacc;
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+      xin[u] = x[u];
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (tile_in[u] && m[c] == 0.f) xin[u][c] = ws[slot(l, u, c)];
+    }
+    masked(xin, m, xm);
+    NvAct h;
+    nv_mlp_fwd<PK>(sW + M::SNET, ln, temb, xm, h, out);
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+      gso[u] = gto[u] = gacc[u] = es[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const float keep = 1.f - m[c];
+        float th, sk, ek, tk;
+        nvp_couple1(tt[u], hard, expf(sfw[c]), keep, out[u][c], 0.f, th, sk, ek, tk);
+        const float cc = hard ? tt[u] : 1.f;
+        const float gs = fmaf(g[u][c], x[u][c], 1.f) * keep;
+        es[u][c] = ek;
+        gso[u][c] = cc * gs * (1.f - th * th);
+        gto[u][c] = cc * g[u][c] * ek * keep;
+      }
+    }
+    nv_mlp_bwd_in<PK>(sW + M::SNET, ln, h, gso, gacc);
+    nv_mlp_fwd<PK>(sW + M::TNET, ln, temb, xm, h, out);
+    nv_mlp_bwd_in<PK>(sW + M::TNET, ln, h, gto, gacc);
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) g[u][c] = fmaf(m[c], gacc[u][c], g[u][c] * es[u][c]);
+      x[u] = xin[u];
+    }
+  }
+  // ---- the score, from the owning lanes ----
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) {
+    const int64_t i = base + 16 * u + ln.s;
+    if (i < n) {
+      float* sr = score + i * ld_s;
+      if constexpr (PK) {
+        if (ln.g < d) sr[ln.g] = g[u][0];
+      } else {
+        if (s_vec && 4 * ln.g + 3 < d) {
+          *reinterpret_cast<f32x4*>(sr + 4 * ln.g) = g[u];
+        } else {
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (4 * ln.g + c < d) sr[4 * ln.g + c] = g[u][c];
+        }
+      }
+    }
+  }
+}
+
 static int64_t layer_params(int D, int in_dim) {
   const int64_t mlp = (int64_t)in_dim * 8 + 8 + 8 * 16 + 16 + 16 * 16 + 16 + 16 * D + D;
   return D + 2 * mlp;
@@ -1890,6 +2434,14 @@ static NvpArgs nvp_args(const pdeinv_realnvp_desc* d) {
   for (int k = 0; k < D * D; ++k) a.inv_cov[k] = d->base_inv_cov[k];
   for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
   return a;
+}
+
+// The embedding's frequencies by position (NvFreq)
+static NvFreq nvp_freq(const NvpArgs& a) {
+  NvFreq fr{};
+  for (int q = 0; q < a.E; ++q)
+    fr.w[q] = (float)exp(-(log(10000.0) / (double)(a.E / 2 - 1)) * (double)(q % (a.E / 2)));
+  return fr;
 }
 
 }  // namespace pdeinv
@@ -2024,9 +2576,7 @@ static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, co
                  PDEINV_ERR_INVALID, "realnvp_time_derivs: misaligned pointer (d_ds needs 8 bytes, the others 4)");
   const int D = d->dim;
   const NvpArgs a = nvp_args(d);
-  NvFreq fr{};
-  for (int q = 0; q < a.E; ++q)
-    fr.w[q] = (float)exp(-(log(10000.0) / (double)(a.E / 2 - 1)) * (double)(q % (a.E / 2)));
+  const NvFreq fr = nvp_freq(a);
   const int64_t ls = layer_params(D, a.in_dim);
   hipStream_t st = (hipStream_t)stream;
   PDEINV_REQUIRE(g_nvp_time_impl != 2 || nvp_time_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,
@@ -2138,4 +2688,91 @@ extern "C" int pdeinv_realnvp_map(const pdeinv_realnvp_desc* d, const float* par
 #undef DIMS
 #undef CASE
   return check_launch("realnvp_map_kernel");
+}
+
+// ---- the score grad_x log p_t(x) (pdeinv_realnvp_score) ----
+// The matrix-core path's envelope: the map's (celu / elu; any dim <= 8, any E, ignore_time; packed layout where
+// nvp_packed holds, identity layout otherwise).
+static bool nvp_score_mfma_ok(const pdeinv_realnvp_desc* d) { return nvp_map_mfma_ok(d); }
+// AUTO's rule, a choice made by measurement: the matrix-core path where it measured faster than
+// the general path on every batch of tools/nvp_score_bench.py, which is its whole envelope (2.2 - 4.9 x).
+static bool nvp_score_auto_mfma(const pdeinv_realnvp_desc* d) { return nvp_score_mfma_ok(d); }
+
+// 0 general, 1 matrix-core, or a negative status (who: the entry point's message prefix)
+#define NVP_SCORE_PATH(d, impl, who, path)                                                                   \
+  NVP_REQUIRE_DESC(d, who);                                                                                  \
+  PDEINV_REQUIRE((impl) == PDEINV_NVP_TIME_AUTO || (impl) == PDEINV_NVP_TIME_GENERAL ||                      \
+                     (impl) == PDEINV_NVP_TIME_MATRIX,                                                       \
+                 PDEINV_ERR_INVALID, who ": impl must be PDEINV_NVP_TIME_AUTO, _GENERAL or _MATRIX");        \
+  PDEINV_REQUIRE((impl) != PDEINV_NVP_TIME_MATRIX || nvp_score_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,           \
+                 who ": the matrix-core path takes celu / elu flows");                                       \
+  const int path = (impl) == PDEINV_NVP_TIME_MATRIX || ((impl) == PDEINV_NVP_TIME_AUTO && nvp_score_auto_mfma(d)) ? 1 : 0
+
+extern "C" int pdeinv_realnvp_score_path(const pdeinv_realnvp_desc* d, int32_t impl) {
+  NVP_SCORE_PATH(d, impl, "realnvp_score_path", path);
+  return path;
+}
+
+// The kept layer inputs. General path: [n_layers][dim][n] floats; matrix-core path: [n_layers][NC][tiles of 16
+// samples][64 lanes] floats, NC = 1 coordinate register in the packed layout, 4 in the identity layout. 0 for
+// arguments the entry point refuses.
+extern "C" size_t pdeinv_realnvp_score_workspace_bytes(const pdeinv_realnvp_desc* d, int64_t n, int32_t impl) {
+  if (!d || d->dim < 1 || d->dim > 8 || d->n_layers < 1 || d->n_layers > PDEINV_REALNVP_MAX_LAYERS || n < 0 ||
+      impl < PDEINV_NVP_TIME_AUTO || impl > PDEINV_NVP_TIME_MATRIX)
+    return 0;
+  if (impl == PDEINV_NVP_TIME_MATRIX && !nvp_score_mfma_ok(d)) return 0;
+  if (impl == PDEINV_NVP_TIME_MATRIX || (impl == PDEINV_NVP_TIME_AUTO && nvp_score_auto_mfma(d)))
+    return (size_t)d->n_layers * (nvp_packed(d) ? 1 : 4) * (size_t)((n + 15) / 16) * 64 * sizeof(float);
+  return (size_t)d->n_layers * (size_t)d->dim * (size_t)n * sizeof(float);
+}
+
+extern "C" int pdeinv_realnvp_score(const pdeinv_realnvp_desc* d, const float* params, const float* t,
+                                    int64_t t_stride, const float* x, int64_t n, int64_t ld, int32_t impl,
+                                    float* score, int64_t ld_s, float* logp, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  NVP_SCORE_PATH(d, impl, "realnvp_score", path);
+  if (ld_s == 0) ld_s = d->dim;
+  PDEINV_REQUIRE(n >= 0 && ld >= d->dim && ld_s >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID,
+                 "realnvp_score: bad sizes (n >= 0, ld_x >= dim, ld_s >= dim or 0, t_stride >= 0)");
+  PDEINV_REQUIRE(n <= (int64_t)0x7FFFFFFF * 128, PDEINV_ERR_INVALID, "realnvp_score: too many samples");
+  PDEINV_REQUIRE((((uintptr_t)params | (uintptr_t)t | (uintptr_t)x | (uintptr_t)score | (uintptr_t)logp |
+                   (uintptr_t)workspace) & 3) == 0,
+                 PDEINV_ERR_INVALID, "realnvp_score: misaligned pointer (4 bytes)");
+  if (n == 0) return PDEINV_OK;
+  PDEINV_REQUIRE(score || logp, PDEINV_ERR_INVALID, "realnvp_score: no output requested (d_score, d_logp both null)");
+  PDEINV_REQUIRE(params && t && x, PDEINV_ERR_INVALID, "realnvp_score: null device pointer");
+  PDEINV_REQUIRE(!score || (workspace && workspace_bytes >= pdeinv_realnvp_score_workspace_bytes(d, n, impl)),
+                 PDEINV_ERR_INVALID, "realnvp_score: workspace too small (pdeinv_realnvp_score_workspace_bytes)");
+  const int D = d->dim;
+  const NvpArgs a = nvp_args(d);
+  const NvFreq fr = nvp_freq(a);
+  const int64_t ls = layer_params(D, a.in_dim);
+  hipStream_t st = (hipStream_t)stream;
+  if (path == 1) {
+    const dim3 g(grid_for(n, kNvSPB));
+    const int s_vec = score && ld_s % 4 == 0 && ((uintptr_t)score & 15) == 0 ? 1 : 0;
+    const int64_t n_tiles = (n + 15) / 16;
+    if (nvp_packed(d))
+      hipLaunchKernelGGL(realnvp_score_mfma_kernel<true>, g, dim3(kBlock), 0, st, a, fr, D, params, t, t_stride, x, n,
+                         ld, ls, score, ld_s, s_vec, logp, (float*)workspace, n_tiles);
+    else
+      hipLaunchKernelGGL(realnvp_score_mfma_kernel<false>, g, dim3(kBlock), 0, st, a, fr, D, params, t, t_stride, x, n,
+                         ld, ls, score, ld_s, s_vec, logp, (float*)workspace, n_tiles);
+    return check_launch("realnvp_score_mfma_kernel");
+  }
+  const dim3 g(grid_for(n));
+  // one instantiation per (dim, activation); celu and elu (alpha = 1) are the same map
+#define CASE(DD, AA) case DD: hipLaunchKernelGGL((realnvp_score_kernel<DD, AA>), g, dim3(kBlock), 0, st, a, fr, params, t, t_stride, x, n, ld, ls, score, ld_s, logp, (float*)workspace); break;
+#define DIMS(AA) switch (D) { CASE(1, AA) CASE(2, AA) CASE(3, AA) CASE(4, AA) CASE(5, AA) CASE(6, AA) CASE(7, AA) CASE(8, AA) }
+  switch (a.act) {
+    case PDEINV_ACT_CELU: case PDEINV_ACT_ELU: DIMS(PDEINV_ACT_CELU) break;
+    case PDEINV_ACT_RELU: DIMS(PDEINV_ACT_RELU) break;
+    case PDEINV_ACT_TANH: DIMS(PDEINV_ACT_TANH) break;
+    case PDEINV_ACT_SILU: DIMS(PDEINV_ACT_SILU) break;
+    case PDEINV_ACT_SOFTPLUS: DIMS(PDEINV_ACT_SOFTPLUS) break;
+    default: DIMS(PDEINV_ACT_GELU) break;
+  }
+#undef DIMS
+#undef CASE
+  return check_launch("realnvp_score_kernel");
 }

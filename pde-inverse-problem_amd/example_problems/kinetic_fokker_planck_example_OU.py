@@ -170,6 +170,14 @@ class KineticFokkerPlanck(ProblemInstance):
             raise ValueError("x should be either 1D (unbatched) or 2D (batched) array.")
         return self.potential.value(x)
 
+    def x_marginal(self, taus):
+        """(mean [n_t, d], cov [n_t, d, d]) in fp64 of the X-marginal N(m1(t), P11(t)) at the time stamps `taus`: the
+        X block of the closed-form moments (kinetic_mckean_vlasov_example_quadratic._mean_cov_stamps)."""
+        from example_problems.kinetic_mckean_vlasov_example_quadratic import _mean_cov_stamps
+        mean, cov = _mean_cov_stamps(taus, self.initial_configuration)
+        d = self.dim
+        return np.ascontiguousarray(mean[:, :d]), np.ascontiguousarray(cov[:, :d, :d])
+
     def exact_sampler(self):
         """The device exact sampler over distribution_time's range (built once per problem)."""
         if getattr(self, "_exact_sampler", None) is None:

@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "pdeinv_mf_mlp_supported", "pdeinv_mf_mlp_workspace_bytes", "pdeinv_mf_mlp_prepare", "pdeinv_mf_mlp_force",
     "pdeinv_mf_mlp_step",
     "pdeinv_realnvp_map_path", "pdeinv_realnvp_map",
+    "pdeinv_realnvp_score_path", "pdeinv_realnvp_score_workspace_bytes", "pdeinv_realnvp_score",
 )
 
 
@@ -222,6 +223,9 @@ def lib():
         "pdeinv_realnvp_time_impl": (i32, [P, i32]),
         "pdeinv_realnvp_map_path": (i32, [P, i32]),
         "pdeinv_realnvp_map": (i32, [P, P, P, i64, P, i64, i64, i32, i32, P, i64, P, P, P]),
+        "pdeinv_realnvp_score_path": (i32, [P, i32]),
+        "pdeinv_realnvp_score_workspace_bytes": (ctypes.c_size_t, [P, i64, i32]),
+        "pdeinv_realnvp_score": (i32, [P, P, P, i64, P, i64, i64, i32, P, i64, P, P, ctypes.c_size_t, P]),
         "pdeinv_kmv_weights_from_ds_workspace_bytes": (ctypes.c_size_t, [i64, i64, i32]),
         "pdeinv_kmv_weights_from_ds": (i32, [i32, f32, P, P, i64, i64, i64, i64, P, P, P]),
         "pdeinv_realnvp_grad_workspace": (i64, [P, i64]),
@@ -1305,6 +1309,51 @@ def realnvp_map(desc, params: torch.Tensor, t: torch.Tensor, x: torch.Tensor, re
                                     0 if t.numel() == 1 else 1, px, n, ld, int(bool(reverse)), _map_impl(impl), py,
                                     ld_y, _dev(res.get("ldj"), "ldj"), _dev(res.get("logp"), "logp"),
                                     stream_handle()), "pdeinv_realnvp_map")
+    return res
+
+
+def realnvp_score_path(desc, impl="auto") -> str:
+    """The path realnvp_score takes for `desc` under `impl` ("auto" / "general" / "matrix"): "general" or "matrix"
+    (pdeinv_realnvp_score_path; stateless, no device call)."""
+    rc = int(lib().pdeinv_realnvp_score_path(ctypes.byref(desc) if desc is not None else None, _map_impl(impl)))
+    _check(min(rc, 0), "pdeinv_realnvp_score_path")
+    return NVP_MAP_PATHS[rc]
+
+
+def realnvp_score(desc, params: torch.Tensor, t: torch.Tensor, x: torch.Tensor, impl="auto", out=None,
+                  want=("score", "logp")):
+    """The score grad_x log p_t(x) of the flow and log p_t(x) itself (pdeinv_realnvp_score) over rows x [n, dim] (a
+    strided row view is honoured) and times t [n] (or a single t, broadcast). Returns {"score": [n, dim], "logp": [n]}
+    restricted to `want`. `out`: a [n, dim] row view (unit inner stride) to write the score into. The workspace (the
+    layers' kept inputs) is allocated here."""
+    _require_gpu()
+    n = x.shape[0]
+    _time_derivs_params(desc, params)
+    want = tuple(want)
+    if not want or any(w not in ("score", "logp") for w in want):
+        raise ValueError("RealNVP score: want must name at least one of 'score', 'logp'")
+    t = t.reshape(-1)
+    if t.numel() not in (1, n):
+        raise ValueError("RealNVP: t must have one entry per row or a single entry")
+    px, _, ld = _rows(x, "x", desc.dim)
+    impl = _map_impl(impl)
+    res, ps, ld_s, ws, ws_bytes = {}, None, 0, None, 0
+    if "score" in want or out is not None:
+        if out is None:
+            out = torch.empty((n, desc.dim), device=x.device, dtype=torch.float32)
+        ps, ns, ld_s = _rows(out, "out", desc.dim)
+        if ns != n:
+            raise ValueError(f"RealNVP score: out must have {n} rows")
+        res["score"] = out
+        ws_bytes = int(lib().pdeinv_realnvp_score_workspace_bytes(ctypes.byref(desc), n, impl))
+        ws = torch.empty(max(ws_bytes, 4) // 4, device=x.device, dtype=torch.float32)
+    if "logp" in want:
+        res["logp"] = torch.empty(n, device=x.device, dtype=torch.float32)
+    t = t.contiguous()
+    _check(lib().pdeinv_realnvp_score(ctypes.byref(desc), _dev(params, "params"), _dev(t, "t"),
+                                      0 if t.numel() == 1 else 1, px, n, ld, impl, ps, ld_s,
+                                      _dev(res.get("logp"), "logp"), _dev(ws, "workspace"), ws_bytes,
+                                      stream_handle()), "pdeinv_realnvp_score")
     return res
 
 
