@@ -52,7 +52,8 @@ extern "C" {
  * pdeinv_sde_simulate_mlp(_supported, _workspace_bytes); PDEINV_POT_MEANFIELD_MLP,
  * pdeinv_mf_mlp_supported, pdeinv_mf_mlp_workspace_bytes, pdeinv_mf_mlp_prepare, pdeinv_mf_mlp_force,
  * pdeinv_mf_mlp_step; pdeinv_realnvp_map, pdeinv_realnvp_map_path; pdeinv_realnvp_score,
- * pdeinv_realnvp_score_path, pdeinv_realnvp_score_workspace_bytes (additive as well: the version stays 10). */
+ * pdeinv_realnvp_score_path, pdeinv_realnvp_score_workspace_bytes; pdeinv_sde_simulate_mlp_wide(_supported,
+ * _workspace_bytes), pdeinv_mlp_potential_wide(_workspace_bytes) (additive as well: the version stays 10). */
 #define PDEINV_MAX_DIM 16          /* d (configuration-space dimension) */
 #define PDEINV_MAX_PARAMS 256      /* floats of potential parameters passed by value */
 
@@ -574,6 +575,20 @@ int pdeinv_gmm_potential(int32_t dim, int32_t n_centers, float sigma, const floa
  * shape->dim. Only the tile envelope is supported (pdeinv_sde_simulate_mlp_supported; else UNSUPPORTED).
  * Fused moments are not offered: take pdeinv_moments of the outputs.
  * Workspace: pdeinv_sde_simulate_mlp_workspace_bytes, 256-byte aligned.
+ *
+ * pdeinv_sde_simulate_mlp_wide — the same call, contract, streams and alignment rules for wide nets: dim <= 8,
+ * 21 <= width <= 256 (zero-padded to Wp = 16 * ceil(width / 16)), n_layers >= 1 with Wp * n_layers <= 512
+ * (256 x 2, 128 x 4, 64 x 8, 32 x 8), out_features <= 64 (pdeinv_sde_simulate_mlp_wide_supported needs no GPU;
+ * outside: UNSUPPORTED, width <= 20 included — those nets belong to pdeinv_sde_simulate_mlp). One launch of
+ * persistent blocks; q and p in registers and the activations in LDS across all n_steps + 1 updates; a weight image
+ * larger than LDS cycles through it in slices. tau is pdeinv_sde_simulate's bit for bit, the noise is the stream
+ * above bit for bit; deterministic, no atomics, any sharding of the particles over calls gives the same bits.
+ * Workspace: pdeinv_sde_simulate_mlp_wide_workspace_bytes (0 outside the envelope), 256-byte aligned.
+ *
+ * pdeinv_mlp_potential_wide — pdeinv_mlp_potential's arguments and outputs through the forward / reverse device
+ * code of pdeinv_sde_simulate_mlp_wide's drift (its direct test, and a second implementation beside path 1 of
+ * pdeinv_mlp_potential, whose path choice does not change). Same envelope as the wide simulator.
+ * Workspace: pdeinv_mlp_potential_wide_workspace_bytes(shape, n), 256-byte aligned.
  * --------------------------------------------------------------------------------------- */
 typedef struct { int32_t dim, n_layers, width, out_features; } pdeinv_mlp_shape;
 int pdeinv_mlp_potential_path(const pdeinv_mlp_shape* shape);
@@ -585,6 +600,14 @@ size_t pdeinv_sde_simulate_mlp_workspace_bytes(const pdeinv_sde_desc* desc, cons
 int pdeinv_sde_simulate_mlp(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape, const float* d_params,
                             const float* d_z0, float* d_traj, float* d_tau, float* d_last, void* d_workspace,
                             void* stream);
+int pdeinv_sde_simulate_mlp_wide_supported(const pdeinv_mlp_shape* shape);
+size_t pdeinv_sde_simulate_mlp_wide_workspace_bytes(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape);
+int pdeinv_sde_simulate_mlp_wide(const pdeinv_sde_desc* desc, const pdeinv_mlp_shape* shape, const float* d_params,
+                                 const float* d_z0, float* d_traj, float* d_tau, float* d_last, void* d_workspace,
+                                 void* stream);
+size_t pdeinv_mlp_potential_wide_workspace_bytes(const pdeinv_mlp_shape* shape, int64_t n);
+int pdeinv_mlp_potential_wide(const pdeinv_mlp_shape* shape, const float* d_params, const float* d_x, int64_t n,
+                              int64_t ld, float* d_value, float* d_grad, void* d_workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * The learned interaction Phi_theta = V_hypothesis of the kinetic McKean–Vlasov system

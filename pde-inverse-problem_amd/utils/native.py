@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "pdeinv_kmv_weights_from_ds_workspace_bytes", "pdeinv_kmv_weights_from_ds",
     "pdeinv_mlp_potential_path", "pdeinv_mlp_potential_workspace_bytes", "pdeinv_mlp_potential",
     "pdeinv_sde_simulate_mlp_supported", "pdeinv_sde_simulate_mlp_workspace_bytes", "pdeinv_sde_simulate_mlp",
+    "pdeinv_sde_simulate_mlp_wide_supported", "pdeinv_sde_simulate_mlp_wide_workspace_bytes",
+    "pdeinv_sde_simulate_mlp_wide", "pdeinv_mlp_potential_wide_workspace_bytes", "pdeinv_mlp_potential_wide",
     "pdeinv_mf_mlp_supported", "pdeinv_mf_mlp_workspace_bytes", "pdeinv_mf_mlp_prepare", "pdeinv_mf_mlp_force",
     "pdeinv_mf_mlp_step",
     "pdeinv_realnvp_map_path", "pdeinv_realnvp_map",
@@ -245,6 +247,11 @@ def lib():
         "pdeinv_sde_simulate_mlp_supported": (ctypes.c_int, [P]),
         "pdeinv_sde_simulate_mlp_workspace_bytes": (ctypes.c_size_t, [P, P]),
         "pdeinv_sde_simulate_mlp": (i32, [P, P, P, P, P, P, P, P, P]),
+        "pdeinv_sde_simulate_mlp_wide_supported": (ctypes.c_int, [P]),
+        "pdeinv_sde_simulate_mlp_wide_workspace_bytes": (ctypes.c_size_t, [P, P]),
+        "pdeinv_sde_simulate_mlp_wide": (i32, [P, P, P, P, P, P, P, P, P]),
+        "pdeinv_mlp_potential_wide_workspace_bytes": (ctypes.c_size_t, [P, i64]),
+        "pdeinv_mlp_potential_wide": (i32, [P, P, P, i64, i64, P, P, P, P]),
         "pdeinv_mf_mlp_supported": (ctypes.c_int, [P]),
         "pdeinv_mf_mlp_workspace_bytes": (ctypes.c_size_t, [P, i64, i64]),
         "pdeinv_mf_mlp_prepare": (i32, [P, P, P, P]),
@@ -453,6 +460,17 @@ def mlp_potential(dims, params_flat: torch.Tensor, x: torch.Tensor, value: bool 
     """V_theta(x_r) and grad V_theta(x_r) of the V_hypothesis MLP (core/model.py:32-62) over the rows of x [n, d]
     (unit inner stride, any row stride) — pdeinv_mlp_potential. params_flat: the device flat flax vector, read
     on the current stream. Returns (value [n] or None, grad [n, d] or None)."""
+    return _mlp_potential("pdeinv_mlp_potential", dims, params_flat, x, value, grad)
+
+
+def mlp_potential_wide(dims, params_flat: torch.Tensor, x: torch.Tensor, value: bool = True, grad: bool = True):
+    """mlp_potential through the wide 16-particle tile (pdeinv_mlp_potential_wide: width 21..256, the drift code of
+    sde_simulate_mlp_wide). Same arguments and returns."""
+    return _mlp_potential("pdeinv_mlp_potential_wide", dims, params_flat, x, value, grad)
+
+
+def _mlp_potential(entry: str, dims, params_flat: torch.Tensor, x: torch.Tensor, value: bool, grad: bool):
+    # serves pdeinv_mlp_potential (mlp_potential) and pdeinv_mlp_potential_wide (mlp_potential_wide): same arguments
     _require_gpu()
     shape = mlp_shape(dims)
     d = shape.dim
@@ -461,10 +479,10 @@ def mlp_potential(dims, params_flat: torch.Tensor, x: torch.Tensor, value: bool 
     xp, _, ld = _rows(x, "x", d) if n > 0 else (None, 0, d)
     v = torch.empty(n, device=x.device, dtype=torch.float32) if value else None
     g = torch.empty((n, d), device=x.device, dtype=torch.float32) if grad else None
-    nbytes = lib().pdeinv_mlp_potential_workspace_bytes(ctypes.byref(shape), n)
+    nbytes = getattr(lib(), entry + "_workspace_bytes")(ctypes.byref(shape), n)
     ws = torch.empty(max(nbytes // 4, 64), device=x.device, dtype=torch.float32)
-    _check(lib().pdeinv_mlp_potential(ctypes.byref(shape), pp, xp, n, ld, _dev(v, "value"), _dev(g, "grad"),
-                                      _dev(ws, "workspace"), stream_handle()), "pdeinv_mlp_potential")
+    _check(getattr(lib(), entry)(ctypes.byref(shape), pp, xp, n, ld, _dev(v, "value"), _dev(g, "grad"),
+                                 _dev(ws, "workspace"), stream_handle()), entry)
     return v, g
 
 
@@ -475,6 +493,37 @@ def sde_simulate_mlp(z0: torch.Tensor, n_steps: int, dt: float, gamma: float, di
                      last: bool = True, out: Optional[dict] = None) -> dict:
     """utils/sampling_utils.py:25-52 with grad U = grad V_theta, the learned V_hypothesis (pdeinv_sde_simulate_mlp):
     sde_simulate's contract and streams, params_flat the device flat flax vector. Time-major traj [n, N, 2d]."""
+    return _sde_simulate_mlp("pdeinv_sde_simulate_mlp", z0, n_steps, dt, gamma, dims, params_flat, seed,
+                             counter_offset, particle_offset, noise_scale, random_shift, noise, shift_u, traj, tau,
+                             last, out)
+
+
+def sde_simulate_mlp_supported(dims) -> bool:
+    """Whether pdeinv_sde_simulate_mlp takes this net (dim <= 8, width <= 20, n_layers <= 8). Needs no GPU."""
+    return bool(lib().pdeinv_sde_simulate_mlp_supported(ctypes.byref(mlp_shape(dims))))
+
+
+def sde_simulate_mlp_wide_supported(dims) -> bool:
+    """Whether pdeinv_sde_simulate_mlp_wide / pdeinv_mlp_potential_wide take this net (dim <= 8, width 21..256,
+    padded width x n_layers <= 512, out_features <= 64). Needs no GPU."""
+    return bool(lib().pdeinv_sde_simulate_mlp_wide_supported(ctypes.byref(mlp_shape(dims))))
+
+
+def sde_simulate_mlp_wide(z0: torch.Tensor, n_steps: int, dt: float, gamma: float, dims, params_flat: torch.Tensor, *,
+                          seed: int, counter_offset: int = 0, particle_offset: int = 0, noise_scale: float = SQRT2,
+                          random_shift: bool = True, noise: Optional[torch.Tensor] = None,
+                          shift_u: Optional[torch.Tensor] = None, traj: bool = True, tau: bool = True,
+                          last: bool = True, out: Optional[dict] = None) -> dict:
+    """sde_simulate_mlp for wide nets (pdeinv_sde_simulate_mlp_wide): same contract, streams and returns."""
+    return _sde_simulate_mlp("pdeinv_sde_simulate_mlp_wide", z0, n_steps, dt, gamma, dims, params_flat, seed,
+                             counter_offset, particle_offset, noise_scale, random_shift, noise, shift_u, traj, tau,
+                             last, out)
+
+
+def _sde_simulate_mlp(entry: str, z0, n_steps, dt, gamma, dims, params_flat, seed, counter_offset, particle_offset,
+                      noise_scale, random_shift, noise, shift_u, traj, tau, last, out) -> dict:
+    # serves pdeinv_sde_simulate_mlp (sde_simulate_mlp) and pdeinv_sde_simulate_mlp_wide (sde_simulate_mlp_wide):
+    # `entry`, `entry + "_supported"` and `entry + "_workspace_bytes"` have the same signatures in both
     _require_gpu()
     shape = mlp_shape(dims)
     desc, p_host, z0p = _sim_desc(z0, n_steps, dt, gamma, dict(kind=POT_MLP), seed, counter_offset, particle_offset,
@@ -482,19 +531,19 @@ def sde_simulate_mlp(z0: torch.Tensor, n_steps: int, dt: float, gamma: float, di
     if desc.dim != shape.dim:
         raise ValueError(f"q0_p0 has d = {desc.dim}, the net takes d = {shape.dim}")
     pp = _mlp_params(shape, params_flat)
-    if not lib().pdeinv_sde_simulate_mlp_supported(ctypes.byref(shape)):
+    if not getattr(lib(), entry + "_supported")(ctypes.byref(shape)):
         ws = None  # the call below reports the envelope; nothing is launched
         res = {} if out is None else out
     else:
         res = _sim_outputs({} if out is None else out, z0, n_steps, traj, tau, last)
-        nbytes = lib().pdeinv_sde_simulate_mlp_workspace_bytes(ctypes.byref(desc), ctypes.byref(shape))
+        nbytes = getattr(lib(), entry + "_workspace_bytes")(ctypes.byref(desc), ctypes.byref(shape))
         ws = torch.empty(max(nbytes // 4, 64), device=z0.device, dtype=torch.float32)
-    rc = lib().pdeinv_sde_simulate_mlp(
+    rc = getattr(lib(), entry)(
         ctypes.byref(desc), ctypes.byref(shape), pp, z0p, _dev(res.get("traj") if traj else None, "traj"),
         _dev(res.get("tau") if tau else None, "tau"), _dev(res.get("last") if last else None, "last"),
         _dev(ws, "workspace"), stream_handle())
     del p_host
-    _check(rc, "pdeinv_sde_simulate_mlp")
+    _check(rc, entry)
     return res
 
 

@@ -40,10 +40,13 @@ def simulate(q0_p0: torch.Tensor, n_steps: int, dt: float, key: Key, potential_g
             raise ValueError("simulate: moments of an MLPPotential ensemble are taken from the written trajectory "
                              "(traj=True); the learned-potential simulator has no fused moments")
         nd = pot.native_desc()
-        r = native.sde_simulate_mlp(q0_p0, n_steps, dt, gamma_friction, nd["dims"], nd["params"], seed=key.seed,
-                                    counter_offset=counter_offset, particle_offset=particle_offset,
-                                    noise_scale=noise_scale, random_shift=random_shift, noise=noise, shift_u=shift_u,
-                                    traj=traj, tau=tau, last=last or moments, out=out)
+        # a net the narrow simulator does not take but the wide one does goes to the wide one
+        wide = not native.sde_simulate_mlp_supported(nd["dims"]) and native.sde_simulate_mlp_wide_supported(nd["dims"])
+        sim = native.sde_simulate_mlp_wide if wide else native.sde_simulate_mlp
+        r = sim(q0_p0, n_steps, dt, gamma_friction, nd["dims"], nd["params"], seed=key.seed,
+                counter_offset=counter_offset, particle_offset=particle_offset, noise_scale=noise_scale,
+                random_shift=random_shift, noise=noise, shift_u=shift_u, traj=traj, tau=tau, last=last or moments,
+                out=out)
         if moments:
             m = q0_p0.shape[1]
             r["moments"] = torch.stack([native.moments(q0_p0), native.moments(r["traj"].reshape(-1, m)),
