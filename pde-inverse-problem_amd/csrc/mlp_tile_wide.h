@@ -2,7 +2,8 @@
 // Dense(out), sum of squares; dim <= 8, width 21..256 zero-padded to Wp = 16 MB, Wp * n_layers <= 512,
 // out_features <= 64): the forward chain h_l = tanh(h_{l-1} K_l + b_l), y = h_L K_o + b_o and the reverse chain
 // from ybar = 2 y through K_o^T, (1 - h_l^2) and K_l^T to g = grad_x V, V = sum y^2. Used by both kernels of
-// sde_mlp_wide.hip. It reuses ftanh, mfma, lane_dims, allow_lds, take, device_cus and kLdsMax of mlp_tile.h.
+// sde_mlp_wide.hip. It reuses ftanh, mfma, lane_dims, allow_lds, take, device_cus and kLdsMax of mlp_tile.h and the
+// waves' slot sizes of sde_mlp_tile.h.
 //
 // Layout. Every product is a v_mfma_f32_16x16x4_f32 with the particle on lane & 15 (the N column) and the weights
 // as the A operand. The C fragment of a product's output block mo holds feature 16 mo + 4 g + r in register r of
@@ -27,6 +28,7 @@
 #pragma once
 #include "common.h"
 #include "mlp_tile.h"
+#include "sde_mlp_tile.h"
 
 namespace pdeinv {
 namespace mlpw {
@@ -35,6 +37,8 @@ using mlpq::allow_lds;
 using mlpq::device_cus;
 using mlpq::ftanh;
 using mlpq::kLdsMax;
+using mlpq::kSlotG;
+using mlpq::kSlotZ;
 using mlpq::lane_dims;
 using mlpq::mfma;
 using mlpq::take;
@@ -45,8 +49,6 @@ constexpr int kSlice4 = kQS * 64;  // f32x4 per slice
 constexpr int kWavesMax = 8;     // waves per block, at most
 constexpr int kWavesStream = 4;  // waves per block a streamed image needs (two slice registers per thread)
 constexpr int kOBMax = 4;        // output blocks: out_features <= 64
-constexpr int kSlotG = 16 * 16;  // gradient slot: [particle][16 coordinates]
-constexpr int kSlotZ = 16 * 16;  // row slot: [particle][2d], d <= 8
 
 // What the kernels need of the net and its image (kernel argument).
 struct WideNet {
@@ -331,24 +333,6 @@ __device__ __forceinline__ f32x4 wide_grad(const WideNet& t, Feed& f, const f32x
   const f32x4 ga = dot_units(f, lane, al, MB, zero);
   feed_rewind(f);
   return ga;
-}
-
-// The tile's rows [16][M] (M = 2d floats, assembled in `slot`) -> dst, whole rows, n_valid of them: 16-byte pieces
-// when M % 4 == 0 (rows then start on 16-byte boundaries), 8-byte pieces otherwise (M is even).
-__device__ __forceinline__ void store_rows(float* dst, const float* slot, int M, int lane, int n_valid) {
-  const int nf = n_valid * M;
-  if ((M & 3) == 0) {
-    const int c = lane;  // 4 M <= 64 chunks
-    if (4 * c < nf)
-      __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(slot + 4 * c), reinterpret_cast<f32x4*>(dst) + c);
-  } else {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {  // 8 M <= 112 chunks
-      const int c = lane + 64 * it;
-      if (2 * c < nf)
-        __builtin_nontemporal_store(*reinterpret_cast<const f32x2*>(slot + 2 * c), reinterpret_cast<f32x2*>(dst) + c);
-    }
-  }
 }
 
 }  // namespace mlpw

@@ -225,6 +225,15 @@ static inline int build_args(const pdeinv_sde_desc* d, SdeArgs& a) {
   return PDEINV_OK;
 }
 
+// build_args for an entry point whose potential is not the descriptor's (a learned one): the shared descriptor
+// checks; the potential's fields are not read.
+static inline int build_args_without_potential(const pdeinv_sde_desc* d, SdeArgs& a) {
+  pdeinv_sde_desc dd = *d;
+  dd.potential = pdeinv_potential{};
+  dd.potential.kind = PDEINV_POT_NONE;
+  return build_args(&dd, a);
+}
+
 // The interacting ensemble shares one clock: tau0 from global id UINT64_MAX (include/pdeinv.h).
 // Computed on the host with the same Philox so that every rank and every step agrees.
 static inline float shared_tau0_host(const SdeArgs& a, const pdeinv_sde_desc* d) {

@@ -178,11 +178,8 @@ extern "C" int pdeinv_mf_mlp_step(const pdeinv_sde_desc* d, const pdeinv_mlp_sha
   PDEINV_REQUIRE(d->potential.kind == PDEINV_POT_MEANFIELD_MLP, PDEINV_ERR_INVALID,
                  "mf_mlp_step: potential kind must be PDEINV_POT_MEANFIELD_MLP");
   PDEINV_REQUIRE(d->dim == s->dim, PDEINV_ERR_INVALID, "mf_mlp_step: descriptor and shape disagree on dim");
-  pdeinv_sde_desc dd = *d;  // the shared descriptor checks; the potential's fields are not read
-  dd.potential = pdeinv_potential{};
-  dd.potential.kind = PDEINV_POT_NONE;
   SdeArgs sa;
-  rc = build_args(&dd, sa);
+  rc = build_args_without_potential(d, sa);
   if (rc) return rc;
   PDEINV_REQUIRE(step >= 0 && step <= d->n_steps, PDEINV_ERR_INVALID, "mf_mlp_step: s out of range");
   PDEINV_REQUIRE(d->d_shift_u == nullptr, PDEINV_ERR_INVALID,
