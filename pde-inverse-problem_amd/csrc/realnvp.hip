@@ -16,12 +16,19 @@
 //     3's nvp_act_d2) and realnvp_score_mfma_kernel (matrix cores: part 2's likelihood pass and backward sweep without
 //     its weight gradients; helper nv_mlp_bwd_in); nvp_couple1 is the coupling update of both, in both passes.
 // Shared: NvpArgs (masks and the base Gaussian travel in the kernel arguments) and nvp_temb_params by all;
-// the block-level staging nv_lane / nv_stage_* by the four tile kernels; the three-stream arithmetic nvp_act3,
-// NVP_COUPLE3 and NVP_BASE_STORE3 (macros: see there) by the two time kernels; one descriptor
-// check (NVP_REQUIRE_DESC) and one NvpArgs fill (nvp_args) by the host entry points.
-// Still written twice, on purpose: the time embedding's forward (sinusoid, bias, nv_fwdT, celu) in
-// realnvp_grad_kernel, once for the likelihood pass and once for the backward (see the comment at the second), and
-// the three lines of sample addressing (per-sample / sets view) in the two time kernels.
+// the block-level staging nv_lane / nv_stage_* by the four tile kernels; nv_prefetch, nv_masked and nv_group_sum by
+// the gradient, map and score tile kernels, nv_scatter_layer by the gradient and map tile kernels (see "blocks of the
+// tile kernels' bodies"); the three-stream arithmetic nvp_act3, NVP_COUPLE3 and NVP_BASE_STORE3 (macros: see there)
+// by the two time kernels; on the host one descriptor check (NVP_REQUIRE_DESC), one NvpArgs fill (nvp_args), one
+// path choice (NVP_IMPL_PATH over nvp_tile_ok) for the map and the score, and one (dim, activation) launch table
+// (NVP_LAUNCH_DIM_ACT) for the general time and score kernels.
+// Still written out in each kernel, because compiled from one shared definition the kernel's register, spill or LDS
+// figures move (DESIGN.md §13.2 has each figure): in the tile kernels the staging of a layer around nv_scatter_layer
+// (the score kernel's scatter too), the tile load, the time embedding's forward (in realnvp_grad_kernel also a
+// second time for the backward: see the comment there), the base form from a __shfl gather, the owning-lane row
+// store, and realnvp_time_mfma_kernel's sum over the lane groups; in the general path the time embedding and the
+// coupling update of realnvp_logdensity_kernel and realnvp_map_kernel, and the former's base form. Also the three
+// lines of sample addressing (per-sample / sets view) in the two time kernels.
 #include <math.h>
 
 #include "common.h"
@@ -175,7 +182,9 @@ __device__ __forceinline__ float nvp_base_quad(const NvpArgs& a, const float (&x
 
 // The flow as a map, one kernel body over the direction (pdeinv_realnvp_map's general path), with the arithmetic
 // of realnvp_logdensity_kernel statement for statement: <D, 1>'s out is that kernel's, bit for bit. (That kernel is
-// not this body's (REV = 1, no y) case: compiled from this body it moves a 16-float array into LDS, 16 KB per block.)
+// not this body's (REV = 1, no y) case: compiled from this body it moves a 16-float array into LDS, 16 KB per block.
+// The same happens to it with nvp_base_quad in place of its own loop, and a shared time embedding or coupling update
+// moves the register and spill figures of both kernels: DESIGN.md §13.2.)
 //   REV = 1: layers L-1 .. 0, x <- (x + tr) e^s,  ldj += sum s, out = log p0(y) + ldj    (likelihood direction)
 //   REV = 0: layers 0 .. L-1, x <- x e^{-s} - tr, ldj -= sum s, out = log p0(x_in) - ldj (generation)
 // y (row stride ld_y), ldj_out and out are each nullable. y may be xv itself (in place: a thread has read its row
@@ -808,6 +817,50 @@ __device__ __forceinline__ void nv_stage_mask(float* sW, const NvpArgs& a, int l
   }
 }
 
+// ---- blocks of the tile kernels' bodies (gradient, map, score), each defined once. State goes in by reference or
+// parameter, never by capture (a captured x cost the identity-layout gradient kernel 12 bytes of scratch); every one
+// is inlined. DESIGN.md §13.2 lists the blocks that stay written out in a kernel, and why. ----
+// Coupling layer l's raw parameters into registers: one coalesced load per thread and slot, in flight under the
+// previous layer's math.
+__device__ __forceinline__ void nv_prefetch(float (&pre)[kNvPre], const float* layers, int l, int64_t layer_stride) {
+  const float* lp = layers + (int64_t)l * layer_stride;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kNvPre; ++k) {
+    const int q = tid + k * kBlock;
+    pre[k] = q < layer_stride ? lp[q] : 0.f;
+  }
+}
+// The prefetched parameters into the layer image sW through the sDst table (nv_layer_dst). WITH_T: with the
+// transposed copies that the input-gradient products read; without, the forward entries only. Every thread of the
+// block calls; the barriers around it are the caller's.
+template <bool WITH_T>
+__device__ __forceinline__ void nv_scatter_layer(float* sW, const uint32_t* sDst, const float (&pre)[kNvPre],
+                                                 int64_t layer_stride) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kNvPre; ++k) {
+    const int q = tid + k * kBlock;
+    if (q < layer_stride) {
+      const uint32_t t = sDst[q];
+      sW[t & 0xFFFFu] = pre[k];
+      if (WITH_T && (t >> 16) != 0xFFFFu) sW[t >> 16] = pre[k];
+    }
+  }
+}
+// The masked input x m of a layer's nets. Packed layout: the coordinates live in register 0 only.
+template <bool PK>
+__device__ __forceinline__ void nv_masked(const NvV& x, const f32x4& m, NvV& xm) {
+#pragma unroll
+  for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
+}
+// Sum of a per-sample value over the four lane groups (lanes s, 16 + s, 32 + s, 48 + s), in every one of them
+__device__ __forceinline__ float nv_group_sum(float v) {
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
 template <bool PK>
 __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_grad_kernel(NvpArgs a, int d, const float* __restrict__ params,
                                                                  const float* __restrict__ tv, int64_t t_stride,
@@ -854,32 +907,17 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   // thread and slot, in flight under the previous layer's math) and scattered into the padded /
   // transposed layer image through the sDst table. Staging order: L-1 .. 0 (likelihood), 0 .. L-1.
   float pre[kNvPre];
-  auto prefetch = [&](int l) {
-    const float* lp = layers + (int64_t)l * layer_stride;
-#pragma unroll
-    for (int k = 0; k < kNvPre; ++k) {
-      const int q = tid + k * kBlock;
-      pre[k] = q < layer_stride ? lp[q] : 0.f;
-    }
-  };
   int staged = 0;  // layers staged so far
   auto stage_layer = [&](int l) {
     __syncthreads();  // every wave is done with the previous layer
     nv_stage_mask<PK>(sW, a, l, d);
-#pragma unroll
-    for (int k = 0; k < kNvPre; ++k) {
-      const int q = tid + k * kBlock;
-      if (q < layer_stride) {
-        const uint32_t t = sDst[q];
-        sW[t & 0xFFFFu] = pre[k];
-        if ((t >> 16) != 0xFFFFu) sW[t >> 16] = pre[k];
-      }
-    }
+    nv_scatter_layer<true>(sW, sDst, pre, layer_stride);
     ++staged;
-    if (staged < 2 * a.n_layers) prefetch(staged < a.n_layers ? a.n_layers - 1 - staged : staged - a.n_layers);
+    if (staged < 2 * a.n_layers)
+      nv_prefetch(pre, layers, staged < a.n_layers ? a.n_layers - 1 - staged : staged - a.n_layers, layer_stride);
     __syncthreads();
   };
-  prefetch(a.n_layers - 1);
+  nv_prefetch(pre, layers, a.n_layers - 1, layer_stride);
   float* row = slab + (int64_t)blockIdx.x * slab_ld;
   // write this block's reduced partials for the flat range [off, off + len): src(f) -> flush index
   auto flush = [&](int64_t off, int len, auto src) {
@@ -928,8 +966,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
   // Packed layout: the coordinates live in register 0 only (registers 1..3 of x, gx stay exactly 0 through
   // every coupling layer), so the per-coordinate coupling math runs over NC = 1 register.
   constexpr int NC = PK ? 1 : 4;
-  // sf = e^alpha and 1 / sf of the staged layer; the masked input of its nets (x a parameter, not a capture:
-  // captured, it costs the identity-layout kernel 12 bytes of scratch)
+  // sf = e^alpha and 1 / sf of the staged layer
   auto scale = [&](f32x4& sf, f32x4& isf) {
     const f32x4 sfw = nv_vec(sW + NvM<PK>::SF, ln);
 #pragma unroll
@@ -937,10 +974,6 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
       sf[c] = nv_exp(sfw[c]);
       isf[c] = __builtin_amdgcn_rcpf(sf[c]);
     }
-  };
-  auto masked = [](const NvV& x, const f32x4& m, NvV& xm) {
-#pragma unroll
-    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
   };
   if (E > 0) {
     NvV se, he;
@@ -966,7 +999,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
     f32x4 sf, isf;
     scale(sf, isf);
     NvV xm, so, to;
-    masked(x, m, xm);
+    nv_masked<PK>(x, m, xm);
     {
       NvAct h;
       nv_mlp_fwd<PK>(sW + NvM<PK>::SNET, ln, temb, xm, h, so);
@@ -1001,9 +1034,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
       quad = fmaf(diff[c], acc, quad);
       gx[u][c] = PK && c > 0 ? 0.f : -w[u] * acc;
     }
-    float part = ldj[u] - 0.5f * quad;  // the four groups' parts sum to log p + 0.5 log_det
-    part += __shfl_xor(part, 16, 64);
-    part += __shfl_xor(part, 32, 64);
+    const float part = nv_group_sum(ldj[u] - 0.5f * quad);  // the four groups' parts sum to log p + 0.5 log_det
     if (ln.g == 0) lsum += w[u] * (part - 0.5f * a.log_det);
   }
   // ---- backward through layers 0 .. L-1, rebuilding each layer's input ----
@@ -1018,7 +1049,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesPk : kNvWaves) void realnvp_gr
     f32x4 galpha = {0.f, 0.f, 0.f, 0.f};
     NvV xm, out, s, es, gso, gto, gacc;
     NvAct h;
-    masked(x, m, xm);
+    nv_masked<PK>(x, m, xm);
     nv_mlp_fwd<PK>(sW + NvM<PK>::SNET, ln, temb, xm, h, out);
 #pragma unroll
     for (int u = 0; u < kNvT; ++u) {
@@ -1649,7 +1680,7 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
 // in the v_mfma_f32_16x16x4_f32 accumulator layout, the layer image NvM<PK> staged through the nv_layer_dst table
 // (the next layer's parameters in registers under this layer's math; no transposed copies), both nets through
 // nv_mlp_fwd<PK>, the coupling update on the lanes that own coordinates, on the hardware exp2 / rcp as in the
-// gradient kernel. A wave carries G groups of kNvT tiles through each staged layer (16 kNvT G samples per wave).
+// gradient kernel. A wave carries kNvT tiles through each staged layer, like its siblings.
 //   REV = 1: staging order L-1 .. 0, x <- (x + tr) e^s,  ldj += sum s, logp = log p0(y) + ldj
 //   REV = 0: staging order 0 .. L-1, x <- x e^{-s} - tr, ldj -= sum s, logp = log p0(x_in) - ldj
 // Base form: every lane gathers its sample's coordinates from the owning lanes (__shfl), as the time kernel does.
@@ -1657,13 +1688,8 @@ __global__ __launch_bounds__(kBlock, kNvWavesTime) void realnvp_time_mfma_kernel
 // 4q .. 4q + 3, one float4 where y_vec says that rows and pointer are 16-byte aligned), lane group 0 ldj and logp.
 // Plain stores, no atomics; a sample's outputs depend on its own column of the tiles only. y may be xv (in place).
 // ---------------------------------------------------------------------------------------------
-#ifndef PDEINV_NVP_MAP_GROUPS
-#define PDEINV_NVP_MAP_GROUPS 1
-#endif
-constexpr int kNvMapG = PDEINV_NVP_MAP_GROUPS;  // groups of kNvT tiles per wave and staged layer
-constexpr int kNvMapSPB = kNvSPB * kNvMapG;     // samples per block
-constexpr int kNvWavesMapPk = 4;                // waves per SIMD, packed layout
-constexpr int kNvWavesMap = 3;                  // waves per SIMD, identity layout (at 4 it spills)
+constexpr int kNvWavesMapPk = 4;  // waves per SIMD, packed layout
+constexpr int kNvWavesMap = 3;    // waves per SIMD, identity layout (at 4 it spills)
 
 template <bool PK, int REV>
 __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void realnvp_map_mfma_kernel(
@@ -1671,7 +1697,6 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void real
     const float* xv, int64_t n, int64_t ld, int64_t layer_stride, float* y, int64_t ld_y, int y_vec,
     float* __restrict__ ldj_out, float* __restrict__ logp_out) {
   using M = NvM<PK>;
-  constexpr int G = kNvMapG;
   constexpr int NC = PK ? 1 : 4;    // registers that hold coordinates
   constexpr int DMAX = PK ? 4 : 8;  // coordinates a layout can hold
   __shared__ float sW[M::LAYER];    // current coupling layer (padded); the time embedding before the first
@@ -1689,15 +1714,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void real
   });
   nv_stage_init<PK>(sDst, sW, layer_stride, d, n_t);
   float pre[kNvPre];
-  auto prefetch = [&](int l) {
-    const float* lp = layers + (int64_t)l * layer_stride;
-#pragma unroll
-    for (int k = 0; k < kNvPre; ++k) {
-      const int q = tid + k * kBlock;
-      pre[k] = q < layer_stride ? lp[q] : 0.f;
-    }
-  };
-  prefetch(REV ? L - 1 : 0);
+  nv_prefetch(pre, layers, REV ? L - 1 : 0, layer_stride);
   __syncthreads();  // sW zeroed
   if (E > 0) nv_stage_temb<PK>(sW, params, E, false);
   __syncthreads();
@@ -1723,64 +1740,52 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void real
     return quad;
   };
   // ---- the wave's tiles ----
-  NvV x[G], temb[G];
-  float tt[G][kNvT], ldj[G][kNvT], quad[G][kNvT];
-  const int64_t base = (int64_t)blockIdx.x * kNvMapSPB + wave * 16 * kNvT * G;
+  NvV x, temb;
+  float tt[kNvT], ldj[kNvT], quad[kNvT];  // quad: the base form of the input (REV = 0)
+  const int64_t base = (int64_t)blockIdx.x * kNvSPB + wave * 16 * kNvT;
 #pragma unroll
-  for (int gi = 0; gi < G; ++gi)
+  for (int u = 0; u < kNvT; ++u) {
+    const int64_t i = base + 16 * u + ln.s;
+    const bool active = i < n;
+    tt[u] = active ? tv[i * t_stride] : 0.f;
 #pragma unroll
-    for (int u = 0; u < kNvT; ++u) {
-      const int64_t i = base + 16 * (gi * kNvT + u) + ln.s;
-      const bool active = i < n;
-      tt[gi][u] = active ? tv[i * t_stride] : 0.f;
+    for (int c = 0; c < 4; ++c) {
+      const int k = nv_xinv<PK>(4 * ln.g + c, d);
+      x[u][c] = (active && k >= 0 && (!PK || c == 0)) ? xv[i * ld + k] : 0.f;  // packed: registers 1..3 are 0
+    }
+    ldj[u] = 0.f;
+    quad[u] = (!REV && logp_out) ? base_quad(x[u]) : 0.f;
+  }
+  if (E > 0) {  // TimeEmbedding (:8-22)
+    NvV se, he;
+#pragma unroll
+    for (int u = 0; u < kNvT; ++u)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int k = nv_xinv<PK>(4 * ln.g + c, d);
-        x[gi][u][c] = (active && k >= 0 && (!PK || c == 0)) ? xv[i * ld + k] : 0.f;  // packed: registers 1..3 are 0
+        const int q = 4 * ln.g + c;
+        const float e = tt[u] * sF[q];
+        se[u][c] = sF[16 + q] * sinf(e) + sF[32 + q] * cosf(e);
       }
-      ldj[gi][u] = 0.f;
-      quad[gi][u] = (!REV && logp_out) ? base_quad(x[gi][u]) : 0.f;
-    }
-  if (E > 0) {  // TimeEmbedding (:8-22)
+    nv_bcast(he, nv_vec(sW + M::E_B1, ln));
+    nv_fwdT(sW + M::E_W1, ln, se, he);
 #pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-      NvV se, he;
-#pragma unroll
-      for (int u = 0; u < kNvT; ++u)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int q = 4 * ln.g + c;
-          const float e = tt[gi][u] * sF[q];
-          se[u][c] = sF[16 + q] * sinf(e) + sF[32 + q] * cosf(e);
-        }
-      nv_bcast(he, nv_vec(sW + M::E_B1, ln));
-      nv_fwdT(sW + M::E_W1, ln, se, he);
-#pragma unroll
-      for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
-      nv_bcast(temb[gi], nv_vec(sW + M::E_B2, ln));
-      nv_fwdT(sW + M::E_W2, ln, he, temb[gi]);
-    }
+    for (int u = 0; u < kNvT; ++u) he[u] = nv_celu4(he[u]);
+    nv_bcast(temb, nv_vec(sW + M::E_B2, ln));
+    nv_fwdT(sW + M::E_W2, ln, he, temb);
     __syncthreads();  // every wave has read the time embedding: back to the zero-padded layer image
     for (int q = tid; q < M::TEMB; q += kBlock) sW[q] = 0.f;
   } else {
 #pragma unroll
-    for (int gi = 0; gi < G; ++gi)
+    for (int u = 0; u < kNvT; ++u)
 #pragma unroll
-      for (int u = 0; u < kNvT; ++u)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          temb[gi][u][c] = (!a.ignore_time && 4 * ln.g + c == nv_tpos<PK>(0)) ? tt[gi][u] : 0.f;
+      for (int c = 0; c < 4; ++c) temb[u][c] = (!a.ignore_time && 4 * ln.g + c == nv_tpos<PK>(0)) ? tt[u] : 0.f;
   }
   for (int j = 0; j < L; ++j) {
     const int l = REV ? L - 1 - j : j;
     __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
     nv_stage_mask<PK>(sW, a, l, d);
-#pragma unroll
-    for (int k = 0; k < kNvPre; ++k) {
-      const int q = tid + k * kBlock;
-      if (q < layer_stride) sW[sDst[q] & 0xFFFFu] = pre[k];
-    }
-    if (j + 1 < L) prefetch(REV ? l - 1 : l + 1);
+    nv_scatter_layer<false>(sW, sDst, pre, layer_stride);
+    if (j + 1 < L) nv_prefetch(pre, layers, REV ? l - 1 : l + 1, layer_stride);
     __syncthreads();
     const f32x4 m = nv_vec(sW + M::MASK, ln);
     const f32x4 sfw = nv_vec(sW + M::SF, ln);
@@ -1790,66 +1795,58 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesMapPk : kNvWavesMap) void real
       sf[c] = nv_exp(sfw[c]);
       isf[c] = __builtin_amdgcn_rcpf(sf[c]);
     }
+    NvV xm, so, to;
+    nv_masked<PK>(x, m, xm);
+    {
+      NvAct h;
+      nv_mlp_fwd<PK>(sW + M::SNET, ln, temb, xm, h, so);
+      nv_mlp_fwd<PK>(sW + M::TNET, ln, temb, xm, h, to);
+    }
 #pragma unroll
-    for (int gi = 0; gi < G; ++gi) {
-      NvV xm, so, to;
+    for (int u = 0; u < kNvT; ++u) {
 #pragma unroll
-      for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[gi][u][0] * m[0], 0.f, 0.f, 0.f} : x[gi][u] * m;
-      {
-        NvAct h;
-        nv_mlp_fwd<PK>(sW + M::SNET, ln, temb[gi], xm, h, so);
-        nv_mlp_fwd<PK>(sW + M::TNET, ln, temb[gi], xm, h, to);
-      }
-#pragma unroll
-      for (int u = 0; u < kNvT; ++u) {
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {  // padded / masked coordinates: keep = 0, x unchanged
-          const float keep = 1.f - m[c];
-          const float th = hard ? tt[gi][u] : 1.f;
-          const float sk = nv_tanh(th * so[u][c] * isf[c]) * sf[c] * keep;
-          const float tr = th * to[u][c] * keep;
-          if (REV) {
-            x[gi][u][c] = (x[gi][u][c] + tr) * nv_exp(sk);
-            ldj[gi][u] += sk;
-          } else {
-            x[gi][u][c] = x[gi][u][c] * nv_exp(-sk) - tr;
-            ldj[gi][u] -= sk;
-          }
+      for (int c = 0; c < NC; ++c) {  // padded / masked coordinates: keep = 0, x unchanged
+        const float keep = 1.f - m[c];
+        const float th = hard ? tt[u] : 1.f;
+        const float sk = nv_tanh(th * so[u][c] * isf[c]) * sf[c] * keep;
+        const float tr = th * to[u][c] * keep;
+        if (REV) {
+          x[u][c] = (x[u][c] + tr) * nv_exp(sk);
+          ldj[u] += sk;
+        } else {
+          x[u][c] = x[u][c] * nv_exp(-sk) - tr;
+          ldj[u] -= sk;
         }
       }
     }
   }
   // ---- outputs ----
 #pragma unroll
-  for (int gi = 0; gi < G; ++gi)
-#pragma unroll
-    for (int u = 0; u < kNvT; ++u) {
-      const int64_t i = base + 16 * (gi * kNvT + u) + ln.s;
-      const bool active = i < n;
-      float lj = ldj[gi][u];  // the four lane groups' parts
-      lj += __shfl_xor(lj, 16, 64);
-      lj += __shfl_xor(lj, 32, 64);
-      float lp = 0.f;
-      if (logp_out) lp = REV ? -0.5f * (a.log_det + base_quad(x[gi][u])) + lj : -0.5f * (a.log_det + quad[gi][u]) - lj;
-      if (active && ln.g == 0) {
-        if (ldj_out) ldj_out[i] = lj;
-        if (logp_out) logp_out[i] = lp;
-      }
-      if (active && y) {
-        float* yr = y + i * ld_y;
-        if constexpr (PK) {
-          if (ln.g < d) yr[ln.g] = x[gi][u][0];
+  for (int u = 0; u < kNvT; ++u) {
+    const int64_t i = base + 16 * u + ln.s;
+    const bool active = i < n;
+    const float lj = nv_group_sum(ldj[u]);  // the four lane groups' parts
+    float lp = 0.f;
+    if (logp_out) lp = REV ? -0.5f * (a.log_det + base_quad(x[u])) + lj : -0.5f * (a.log_det + quad[u]) - lj;
+    if (active && ln.g == 0) {
+      if (ldj_out) ldj_out[i] = lj;
+      if (logp_out) logp_out[i] = lp;
+    }
+    if (active && y) {
+      float* yr = y + i * ld_y;
+      if constexpr (PK) {
+        if (ln.g < d) yr[ln.g] = x[u][0];
+      } else {
+        if (y_vec && 4 * ln.g + 3 < d) {
+          *reinterpret_cast<f32x4*>(yr + 4 * ln.g) = x[u];
         } else {
-          if (y_vec && 4 * ln.g + 3 < d) {
-            *reinterpret_cast<f32x4*>(yr + 4 * ln.g) = x[gi][u];
-          } else {
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
-              if (4 * ln.g + c < d) yr[4 * ln.g + c] = x[gi][u][c];
-          }
+          for (int c = 0; c < 4; ++c)
+            if (4 * ln.g + c < d) yr[4 * ln.g + c] = x[u][c];
         }
       }
     }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2191,14 +2188,6 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void 
     sB[q] = (r >= 0 && c < d) ? 0.5f * (a.inv_cov[r * d + c] + a.inv_cov[c * d + r]) : 0.f;
   }
   float pre[kNvPre];
-  auto prefetch = [&](int l) {
-    const float* lp = layers + (int64_t)l * layer_stride;
-#pragma unroll
-    for (int k = 0; k < kNvPre; ++k) {
-      const int q = tid + k * kBlock;
-      pre[k] = q < layer_stride ? lp[q] : 0.f;
-    }
-  };
   int staged = 0;  // layers staged so far
   auto stage_layer = [&](int l) {
     __syncthreads();  // every wave is done with the previous layer (and the image is zero-padded)
@@ -2213,10 +2202,11 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void 
       }
     }
     ++staged;
-    if (staged < 2 * L && (score || staged < L)) prefetch(staged < L ? L - 1 - staged : staged - L);
+    if (staged < 2 * L && (score || staged < L))
+      nv_prefetch(pre, layers, staged < L ? L - 1 - staged : staged - L, layer_stride);
     __syncthreads();
   };
-  prefetch(L - 1);
+  nv_prefetch(pre, layers, L - 1, layer_stride);
   __syncthreads();  // sW zeroed
   if (E > 0) nv_stage_temb<PK>(sW, params, E, false);
   __syncthreads();
@@ -2266,17 +2256,13 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void 
   bool tile_in[kNvT];
 #pragma unroll
   for (int u = 0; u < kNvT; ++u) tile_in[u] = (base >> 4) + u < n_tiles;
-  auto masked = [](const NvV& x, const f32x4& m, NvV& xm) {
-#pragma unroll
-    for (int u = 0; u < kNvT; ++u) xm[u] = PK ? f32x4{x[u][0] * m[0], 0.f, 0.f, 0.f} : x[u] * m;
-  };
   // ---- likelihood pass (layers L-1 .. 0): x <- (x + tr) e^s ----
   for (int l = L - 1; l >= 0; --l) {
     stage_layer(l);
     const f32x4 m = nv_vec(sW + M::MASK, ln);
     const f32x4 sfw = nv_vec(sW + M::SF, ln);
     NvV xm, so, to;
-    masked(x, m, xm);
+    nv_masked<PK>(x, m, xm);
     {
       NvAct h;
       nv_mlp_fwd<PK>(sW + M::SNET, ln, temb, xm, h, so);
@@ -2323,9 +2309,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void 
       }
       g[u][c] = -acc;
     }
-    float lj = ldj[u];  // the four lane groups' parts
-    lj += __shfl_xor(lj, 16, 64);
-    lj += __shfl_xor(lj, 32, 64);
+    const float lj = nv_group_sum(ldj[u]);  // the four lane groups' parts
     const int64_t i = base + 16 * u + ln.s;
     if (logp_out && i < n && ln.g == 0) logp_out[i] = -0.5f * (a.log_det + quad) + lj;
   }
@@ -2343,7 +2327,7 @@ __global__ __launch_bounds__(kBlock, PK ? kNvWavesScorePk : kNvWavesScore) void 
       for (int c = 0; c < NC; ++c)
         if (tile_in[u] && m[c] == 0.f) xin[u][c] = ws[slot(l, u, c)];
     }
-    masked(xin, m, xm);
+    nv_masked<PK>(xin, m, xm);
     NvAct h;
     nv_mlp_fwd<PK>(sW + M::SNET, ln, temb, xm, h, out);
 #pragma unroll
@@ -2435,6 +2419,29 @@ static NvpArgs nvp_args(const pdeinv_realnvp_desc* d) {
   for (int k = 0; k < d->n_layers * D; ++k) a.masks[k] = d->masks[k];
   return a;
 }
+
+// Launch of a general-path kernel K<D, ACT> (block kBlock, grid g, stream st, then K's arguments): one instantiation
+// per (dim 1 .. 8, activation); celu and elu (alpha = 1) are the same map.
+#define NVP_DIMS_(K, AA, D, g, st, ...)                                                     \
+  switch (D) {                                                                              \
+    case 1: hipLaunchKernelGGL((K<1, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 2: hipLaunchKernelGGL((K<2, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 3: hipLaunchKernelGGL((K<3, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 4: hipLaunchKernelGGL((K<4, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 5: hipLaunchKernelGGL((K<5, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 6: hipLaunchKernelGGL((K<6, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 7: hipLaunchKernelGGL((K<7, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+    case 8: hipLaunchKernelGGL((K<8, AA>), g, dim3(kBlock), 0, st, __VA_ARGS__); break;     \
+  }
+#define NVP_LAUNCH_DIM_ACT(K, D, act, g, st, ...)                                                        \
+  switch (act) {                                                                                         \
+    case PDEINV_ACT_CELU: case PDEINV_ACT_ELU: NVP_DIMS_(K, PDEINV_ACT_CELU, D, g, st, __VA_ARGS__) break; \
+    case PDEINV_ACT_RELU: NVP_DIMS_(K, PDEINV_ACT_RELU, D, g, st, __VA_ARGS__) break;                    \
+    case PDEINV_ACT_TANH: NVP_DIMS_(K, PDEINV_ACT_TANH, D, g, st, __VA_ARGS__) break;                    \
+    case PDEINV_ACT_SILU: NVP_DIMS_(K, PDEINV_ACT_SILU, D, g, st, __VA_ARGS__) break;                    \
+    case PDEINV_ACT_SOFTPLUS: NVP_DIMS_(K, PDEINV_ACT_SOFTPLUS, D, g, st, __VA_ARGS__) break;            \
+    default: NVP_DIMS_(K, PDEINV_ACT_GELU, D, g, st, __VA_ARGS__) break;                                 \
+  }
 
 // The embedding's frequencies by position (NvFreq)
 static NvFreq nvp_freq(const NvpArgs& a) {
@@ -2587,19 +2594,8 @@ static int nvp_time_launch(const pdeinv_realnvp_desc* d, const float* params, co
     return check_launch("realnvp_time_mfma_kernel");
   }
   const dim3 g(grid_for(n));
-  // one instantiation per (dim, activation); celu and elu (alpha = 1) are the same map
-#define CASE(DD, AA) case DD: hipLaunchKernelGGL((realnvp_time_kernel<DD, AA>), g, dim3(kBlock), 0, st, a, fr, params, t, t_stride, x, n, ld, n_rows, set_stride, ls, logp, ds); break;
-#define DIMS(AA) switch (D) { CASE(1, AA) CASE(2, AA) CASE(3, AA) CASE(4, AA) CASE(5, AA) CASE(6, AA) CASE(7, AA) CASE(8, AA) }
-  switch (a.act) {
-    case PDEINV_ACT_CELU: case PDEINV_ACT_ELU: DIMS(PDEINV_ACT_CELU) break;
-    case PDEINV_ACT_RELU: DIMS(PDEINV_ACT_RELU) break;
-    case PDEINV_ACT_TANH: DIMS(PDEINV_ACT_TANH) break;
-    case PDEINV_ACT_SILU: DIMS(PDEINV_ACT_SILU) break;
-    case PDEINV_ACT_SOFTPLUS: DIMS(PDEINV_ACT_SOFTPLUS) break;
-    default: DIMS(PDEINV_ACT_GELU) break;
-  }
-#undef DIMS
-#undef CASE
+  NVP_LAUNCH_DIM_ACT(realnvp_time_kernel, D, a.act, g, st, a, fr, params, t, t_stride, x, n, ld, n_rows, set_stride, ls, logp,
+                     ds);
   return check_launch("realnvp_time_kernel");
 }
 
@@ -2626,35 +2622,35 @@ extern "C" int pdeinv_realnvp_time_impl(const pdeinv_realnvp_desc* d, int32_t im
   return g_nvp_time_impl == 0 && nvp_time_mfma_ok(d) ? 1 : 0;
 }
 
-// ---- the flow as a map (pdeinv_realnvp_map) ----
-// The matrix-core path's envelope: that of pdeinv_realnvp_value_and_grad (celu / elu; any dim <= 8, any E,
-// ignore_time; packed layout where nvp_packed holds, identity layout otherwise).
-static bool nvp_map_mfma_ok(const pdeinv_realnvp_desc* d) {
+// ---- the flow as a map (pdeinv_realnvp_map) and the score (pdeinv_realnvp_score): the path ----
+// The envelope of both matrix-core paths: that of pdeinv_realnvp_value_and_grad (celu / elu; any dim <= 8, any E,
+// ignore_time; packed layout where nvp_packed holds, identity layout otherwise). It is also AUTO's rule, a choice made
+// by measurement: the matrix-core path was faster than the general one on every batch of every descriptor class in
+// the envelope (the map: DESIGN.md §4.2.2; the score: §4.2.3, tools/nvp_score_bench.py, 2.2 - 4.9 x).
+static bool nvp_tile_ok(const pdeinv_realnvp_desc* d) {
   return d->activation == PDEINV_ACT_CELU || d->activation == PDEINV_ACT_ELU;
 }
-// AUTO's rule, a choice made by measurement: the matrix-core path where it measured faster than
-// the general path on every batch of the descriptor class.
-static bool nvp_map_auto_mfma(const pdeinv_realnvp_desc* d) { return nvp_map_mfma_ok(d); }
 
-// 0 general, 1 matrix-core, or a negative status (who: the entry point's message prefix)
-#define NVP_MAP_PATH(d, impl, who, path)                                                                     \
+// The descriptor and impl checks of an entry point of either, then path: 0 general, 1 matrix-core (who: the entry
+// point's message prefix)
+#define NVP_IMPL_PATH(d, impl, who, path)                                                                    \
   NVP_REQUIRE_DESC(d, who);                                                                                  \
   PDEINV_REQUIRE((impl) == PDEINV_NVP_TIME_AUTO || (impl) == PDEINV_NVP_TIME_GENERAL ||                      \
                      (impl) == PDEINV_NVP_TIME_MATRIX,                                                       \
                  PDEINV_ERR_INVALID, who ": impl must be PDEINV_NVP_TIME_AUTO, _GENERAL or _MATRIX");        \
-  PDEINV_REQUIRE((impl) != PDEINV_NVP_TIME_MATRIX || nvp_map_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,             \
+  PDEINV_REQUIRE((impl) != PDEINV_NVP_TIME_MATRIX || nvp_tile_ok(d), PDEINV_ERR_UNSUPPORTED,                 \
                  who ": the matrix-core path takes celu / elu flows");                                       \
-  const int path = (impl) == PDEINV_NVP_TIME_MATRIX || ((impl) == PDEINV_NVP_TIME_AUTO && nvp_map_auto_mfma(d)) ? 1 : 0
+  const int path = (impl) == PDEINV_NVP_TIME_MATRIX || ((impl) == PDEINV_NVP_TIME_AUTO && nvp_tile_ok(d)) ? 1 : 0
 
 extern "C" int pdeinv_realnvp_map_path(const pdeinv_realnvp_desc* d, int32_t impl) {
-  NVP_MAP_PATH(d, impl, "realnvp_map_path", path);
+  NVP_IMPL_PATH(d, impl, "realnvp_map_path", path);
   return path;
 }
 
 extern "C" int pdeinv_realnvp_map(const pdeinv_realnvp_desc* d, const float* params, const float* t, int64_t t_stride,
                                   const float* x, int64_t n, int64_t ld, int32_t reverse, int32_t impl, float* y,
                                   int64_t ld_y, float* ldj, float* logp, void* stream) {
-  NVP_MAP_PATH(d, impl, "realnvp_map", path);
+  NVP_IMPL_PATH(d, impl, "realnvp_map", path);
   PDEINV_REQUIRE(reverse == 0 || reverse == 1, PDEINV_ERR_INVALID, "realnvp_map: reverse must be 0 or 1");
   if (ld_y == 0) ld_y = d->dim;
   PDEINV_REQUIRE(n >= 0 && ld >= d->dim && ld_y >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID,
@@ -2670,7 +2666,7 @@ extern "C" int pdeinv_realnvp_map(const pdeinv_realnvp_desc* d, const float* par
   const int64_t ls = layer_params(D, a.in_dim);
   hipStream_t st = (hipStream_t)stream;
   if (path == 1) {
-    const dim3 g(grid_for(n, kNvMapSPB));
+    const dim3 g(grid_for(n, kNvSPB));
     const int y_vec = y && ld_y % 4 == 0 && ((uintptr_t)y & 15) == 0 ? 1 : 0;
 #define MAPK(PKK, RR) hipLaunchKernelGGL((realnvp_map_mfma_kernel<PKK, RR>), g, dim3(kBlock), 0, st, a, D, params, t, t_stride, x, n, ld, ls, y, ld_y, y_vec, ldj, logp)
     if (nvp_packed(d)) {
@@ -2691,25 +2687,8 @@ extern "C" int pdeinv_realnvp_map(const pdeinv_realnvp_desc* d, const float* par
 }
 
 // ---- the score grad_x log p_t(x) (pdeinv_realnvp_score) ----
-// The matrix-core path's envelope: the map's (celu / elu; any dim <= 8, any E, ignore_time; packed layout where
-// nvp_packed holds, identity layout otherwise).
-static bool nvp_score_mfma_ok(const pdeinv_realnvp_desc* d) { return nvp_map_mfma_ok(d); }
-// AUTO's rule, a choice made by measurement: the matrix-core path where it measured faster than
-// the general path on every batch of tools/nvp_score_bench.py, which is its whole envelope (2.2 - 4.9 x).
-static bool nvp_score_auto_mfma(const pdeinv_realnvp_desc* d) { return nvp_score_mfma_ok(d); }
-
-// 0 general, 1 matrix-core, or a negative status (who: the entry point's message prefix)
-#define NVP_SCORE_PATH(d, impl, who, path)                                                                   \
-  NVP_REQUIRE_DESC(d, who);                                                                                  \
-  PDEINV_REQUIRE((impl) == PDEINV_NVP_TIME_AUTO || (impl) == PDEINV_NVP_TIME_GENERAL ||                      \
-                     (impl) == PDEINV_NVP_TIME_MATRIX,                                                       \
-                 PDEINV_ERR_INVALID, who ": impl must be PDEINV_NVP_TIME_AUTO, _GENERAL or _MATRIX");        \
-  PDEINV_REQUIRE((impl) != PDEINV_NVP_TIME_MATRIX || nvp_score_mfma_ok(d), PDEINV_ERR_UNSUPPORTED,           \
-                 who ": the matrix-core path takes celu / elu flows");                                       \
-  const int path = (impl) == PDEINV_NVP_TIME_MATRIX || ((impl) == PDEINV_NVP_TIME_AUTO && nvp_score_auto_mfma(d)) ? 1 : 0
-
 extern "C" int pdeinv_realnvp_score_path(const pdeinv_realnvp_desc* d, int32_t impl) {
-  NVP_SCORE_PATH(d, impl, "realnvp_score_path", path);
+  NVP_IMPL_PATH(d, impl, "realnvp_score_path", path);
   return path;
 }
 
@@ -2720,8 +2699,8 @@ extern "C" size_t pdeinv_realnvp_score_workspace_bytes(const pdeinv_realnvp_desc
   if (!d || d->dim < 1 || d->dim > 8 || d->n_layers < 1 || d->n_layers > PDEINV_REALNVP_MAX_LAYERS || n < 0 ||
       impl < PDEINV_NVP_TIME_AUTO || impl > PDEINV_NVP_TIME_MATRIX)
     return 0;
-  if (impl == PDEINV_NVP_TIME_MATRIX && !nvp_score_mfma_ok(d)) return 0;
-  if (impl == PDEINV_NVP_TIME_MATRIX || (impl == PDEINV_NVP_TIME_AUTO && nvp_score_auto_mfma(d)))
+  if (impl == PDEINV_NVP_TIME_MATRIX && !nvp_tile_ok(d)) return 0;
+  if (impl == PDEINV_NVP_TIME_MATRIX || (impl == PDEINV_NVP_TIME_AUTO && nvp_tile_ok(d)))
     return (size_t)d->n_layers * (nvp_packed(d) ? 1 : 4) * (size_t)((n + 15) / 16) * 64 * sizeof(float);
   return (size_t)d->n_layers * (size_t)d->dim * (size_t)n * sizeof(float);
 }
@@ -2730,7 +2709,7 @@ extern "C" int pdeinv_realnvp_score(const pdeinv_realnvp_desc* d, const float* p
                                     int64_t t_stride, const float* x, int64_t n, int64_t ld, int32_t impl,
                                     float* score, int64_t ld_s, float* logp, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  NVP_SCORE_PATH(d, impl, "realnvp_score", path);
+  NVP_IMPL_PATH(d, impl, "realnvp_score", path);
   if (ld_s == 0) ld_s = d->dim;
   PDEINV_REQUIRE(n >= 0 && ld >= d->dim && ld_s >= d->dim && t_stride >= 0, PDEINV_ERR_INVALID,
                  "realnvp_score: bad sizes (n >= 0, ld_x >= dim, ld_s >= dim or 0, t_stride >= 0)");
@@ -2761,18 +2740,7 @@ extern "C" int pdeinv_realnvp_score(const pdeinv_realnvp_desc* d, const float* p
     return check_launch("realnvp_score_mfma_kernel");
   }
   const dim3 g(grid_for(n));
-  // one instantiation per (dim, activation); celu and elu (alpha = 1) are the same map
-#define CASE(DD, AA) case DD: hipLaunchKernelGGL((realnvp_score_kernel<DD, AA>), g, dim3(kBlock), 0, st, a, fr, params, t, t_stride, x, n, ld, ls, score, ld_s, logp, (float*)workspace); break;
-#define DIMS(AA) switch (D) { CASE(1, AA) CASE(2, AA) CASE(3, AA) CASE(4, AA) CASE(5, AA) CASE(6, AA) CASE(7, AA) CASE(8, AA) }
-  switch (a.act) {
-    case PDEINV_ACT_CELU: case PDEINV_ACT_ELU: DIMS(PDEINV_ACT_CELU) break;
-    case PDEINV_ACT_RELU: DIMS(PDEINV_ACT_RELU) break;
-    case PDEINV_ACT_TANH: DIMS(PDEINV_ACT_TANH) break;
-    case PDEINV_ACT_SILU: DIMS(PDEINV_ACT_SILU) break;
-    case PDEINV_ACT_SOFTPLUS: DIMS(PDEINV_ACT_SOFTPLUS) break;
-    default: DIMS(PDEINV_ACT_GELU) break;
-  }
-#undef DIMS
-#undef CASE
+  NVP_LAUNCH_DIM_ACT(realnvp_score_kernel, D, a.act, g, st, a, fr, params, t, t_stride, x, n, ld, ls, score, ld_s, logp,
+                     (float*)workspace);
   return check_launch("realnvp_score_kernel");
 }
